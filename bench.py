@@ -8,8 +8,13 @@ random-init weights.  Each step = forward + backward + DP gradient sync + grad-n
 fused AdamW update of ALL parameters (nothing skipped in the timed region).
 
 Usage (driver contract):
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line, nothing else.
+``--dump-outputs DIR`` also writes the last timed step's results as ``DIR/<name>.npy`` (the
+inputs are seeded, so two builds can be compared output for output).  ``--full`` is where any
+measurement beyond the headline figure belongs.
 
 Scaling is *weak*: each GPU processes ``--micro-batch`` sequences per step, so the global
 batch grows with N.  Rank 0 prints one JSON line.
@@ -57,7 +62,44 @@ def parse():
     ap.add_argument("--device", default="auto")
     ap.add_argument("--backend", default="auto", help="auto (RCCL on GPU, gloo on CPU) | nccl | gloo")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks that the headline figure does not need "
+                         "(none at present: a plain run already does only setup, warm-up and the timed steps)")
     return ap.parse_args()
+
+
+DUMP_PER_PARAM = 8192  # elements sampled from each parameter tensor (GPT-7B: 291 tensors, ~9.5 MB of fp32)
+
+
+def dump_outputs(path, eng, out):
+    """What a caller of ``train_step`` receives from the last timed step: its return values
+    (``loss``, ``grad_norm``, ``lr``) and the parameters it updated.  The parameters are
+    written as a fixed sample, ``DUMP_PER_PARAM`` elements of every tensor at indices drawn
+    from a generator seeded with a constant (a tensor no larger than that is written whole),
+    concatenated in ``named_parameters()`` order into ``params_sample.npy``; all float32."""
+    import numpy as np
+    import torch
+
+    eng.optimizer.wait_params()  # the side-stream update / parameter gather of the last step
+    if eng.device.type == "cuda":
+        torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    for name in ("loss", "grad_norm", "lr"):
+        v = out[name]
+        v = v.detach().float().cpu().reshape(-1) if torch.is_tensor(v) else torch.tensor([float(v)])
+        np.save(os.path.join(path, name + ".npy"), v.numpy().astype(np.float32))
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(20240607)
+    parts = []
+    for _, p in eng.model.named_parameters():
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_PER_PARAM:
+            idx = torch.randint(0, flat.numel(), (DUMP_PER_PARAM,), generator=gen)
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    np.save(os.path.join(path, "params_sample.npy"), torch.cat(parts).numpy().astype(np.float32))
 
 
 def main():
@@ -172,6 +214,10 @@ def main():
         "max_mem_gb": round(torch.cuda.max_memory_allocated(dev) / 2**30, 1) if dev.type == "cuda" else None,
         "final_loss": round(loss, 4),
     }
+    if args.dump_outputs and out is not None:
+        eng.optimizer.wait_params()
+        if eng.is_main:
+            dump_outputs(args.dump_outputs, eng, dict(out, loss=loss))  # the pipeline's loss lives on the last stage
     if eng.is_main:
         line = json.dumps(res)
         print(line, flush=True)
