@@ -75,6 +75,8 @@ class PerfKnobs:
     async_decode: bool = True      # pure decode steps pipelined: step N+1 launched (ids fed on the
                                    # device from step N's in-graph sampling) before step N's tokens are read
     tp_fused_decode: bool = True   # TP decode: all-reduce + residual + RMSNorm in one kernel
+    moe_decode_fused: bool = True  # MoE decode MLPs on the routed-expert kernels (moe_decode.hip), in the
+                                   # captured graph; off: the eager MoEMLP module per layer (A/B)
 
     def as_dict(self) -> Dict[str, Any]:
         return dataclasses.asdict(self)

@@ -26,6 +26,11 @@ from .functional import (
     layernorm,
     linear_acc_,
     linear_rowscale,
+    MoEExpertTable,
+    moe_decode_down_add_rmsnorm,
+    moe_decode_ok,
+    moe_decode_up_swiglu,
+    moe_route,
     paged_attention_decode,
     paged_prefill_attention,
     attn_merge_,
@@ -49,4 +54,5 @@ __all__ = [
     "paged_prefill_attention", "prefill_work_list", "attn_merge_",
     "rmsnorm", "rope_qkv", "rope_flash_attention", "rope_qkv_cache", "sample", "swiglu", "transpose_", "up_swiglu",
     "rms_rstd", "linear_rowscale", "up_swiglu_rowscale", "linear_acc_",
+    "MoEExpertTable", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",
 ]

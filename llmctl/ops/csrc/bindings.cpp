@@ -54,6 +54,10 @@ TORCH_LIBRARY(llmctl, m) {
   m.def("decode_linear_partials(Tensor x, Tensor w, Tensor? w_scale=None) -> Tensor");
   m.def("decode_linear_add_rmsnorm(Tensor x, Tensor w, Tensor? bias, Tensor residual, Tensor norm_w, float eps, Tensor? w_scale=None) -> (Tensor, Tensor)");
   m.def("decode_linear_fp8(Tensor x, Tensor w, Tensor w_scale, Tensor? bias) -> Tensor");
+  // routed-expert decode MLP (moe_decode.hip); *_ptrs: int64 [E] device table of expert weight pointers
+  m.def("moe_route(Tensor x, Tensor w_router, int k) -> (Tensor, Tensor)");
+  m.def("moe_decode_up_swiglu(Tensor x, Tensor up_ptrs, Tensor topi, int E, int F) -> Tensor");
+  m.def("moe_decode_down_add_rmsnorm(Tensor act, Tensor down_ptrs, Tensor topi, Tensor topw, Tensor residual, Tensor norm_w, float eps, int E) -> (Tensor, Tensor)");
   m.def("sample(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor uniform) -> Tensor");
   // benchmarks / tuning (gemm_bf16.hip, hbm_stream.hip)
   m.def("gemm_bf16(Tensor a, Tensor b) -> Tensor");

@@ -587,6 +587,80 @@ def decode_linear_add_rmsnorm(x, w, b, residual, norm_w, eps: float, w_scale=Non
     return add_rmsnorm(y, residual, norm_w, eps)
 
 
+# ----------------------------------------------------------------------- routed-expert decode MLP
+# A Mixtral-style MoE layer's MLP half for a decode step (csrc/moe_decode.hip): router top-k ->
+# gate/up + SwiGLU of the routed (token, slot) copies -> down + weighted combine + residual +
+# RMSNorm, all routing on the device (no host sync, no atomics, no data-dependent shapes).
+
+class MoEExpertTable:
+    """One projection's expert weights (``experts_up`` or ``experts_down`` of a ``MoEMLP``) as the
+    kernels take them: a device table of ``data_ptr()``s (int64 ``[E]``), built once, next to the
+    list of tensors it points into (kept alive here).  The model keeps one ``Parameter`` per expert;
+    a stacked copy would double it.  Every expert must be 2-D contiguous, 16-byte aligned, and of
+    one shape, dtype and device."""
+
+    def __init__(self, experts):
+        self.tensors = [e.detach() for e in experts]
+        if not self.tensors:
+            raise ValueError("MoEExpertTable: no experts")
+        t0 = self.tensors[0]
+        for i, t in enumerate(self.tensors):
+            if t.dim() != 2 or not t.is_contiguous():
+                raise ValueError(f"MoEExpertTable: expert {i} must be a contiguous 2-D tensor")
+            if t.shape != t0.shape or t.dtype != t0.dtype or t.device != t0.device:
+                raise ValueError(f"MoEExpertTable: expert {i} is {tuple(t.shape)} {t.dtype} on {t.device}, "
+                                 f"expert 0 is {tuple(t0.shape)} {t0.dtype} on {t0.device}")
+            if t.data_ptr() % 16:
+                raise ValueError(f"MoEExpertTable: expert {i} is not 16-byte aligned")
+        self.E, self.shape, self.dtype, self.device = len(self.tensors), tuple(t0.shape), t0.dtype, t0.device
+        self.ptrs = torch.tensor([t.data_ptr() for t in self.tensors], dtype=torch.int64).to(self.device)
+
+    def stale(self) -> bool:
+        """Has an expert's storage moved since the table was built (e.g. ``module.to(...)``)?"""
+        return self.ptrs.tolist() != [t.data_ptr() for t in self.tensors]
+
+
+def moe_decode_ok(x, E: int, k: int, h: int, F: int) -> bool:
+    """Can a decode step's routed MLP run on the ``csrc/moe_decode.hip`` kernels?  1..64 bf16 token
+    rows on the GPU, <= 64 experts, 1 <= k <= min(E, 8), hidden and expert width multiples of 128,
+    hidden <= 16384 (the final pass stages a row in LDS)."""
+    return (use_native(x) and x.dim() == 2 and x.dtype == torch.bfloat16 and x.is_contiguous()
+            and 1 <= x.shape[0] <= 64 and x.shape[1] == h and 1 <= E <= 64 and 1 <= k <= min(E, 8)
+            and h % 128 == 0 and h <= 16384 and F >= 128 and F % 128 == 0)
+
+
+def _moe_table_ok(x, table: MoEExpertTable) -> bool:
+    return table.dtype == torch.bfloat16 and table.device == x.device
+
+
+def moe_route(x, w_router, k: int):
+    """``(topi int32 [M, k], topw fp32 [M, k])``: softmax (fp32) of the router logits
+    ``linear(x, w_router)`` (rounded to the activation dtype), the k most probable experts per
+    token in descending order (ties: lowest index), weights renormalised over the picks."""
+    E, h = w_router.shape
+    if moe_decode_ok(x, E, k, h, 128) and w_router.dtype == torch.bfloat16 and w_router.is_contiguous():
+        return native().moe_route(x, w_router, k)
+    return ref.moe_route(x, w_router, k)
+
+
+def moe_decode_up_swiglu(x, up: MoEExpertTable, topi):
+    """``act [M k, F]``: row ``t k + j`` is ``silu(g) * u`` of ``x[t] @ W_up[topi[t, j]]^T``
+    (``W_up[e] = [2F, h]``, gate rows first).  Unrouted experts' weights are not read."""
+    F_ = up.shape[0] // 2
+    if moe_decode_ok(x, up.E, topi.shape[1], up.shape[1], F_) and _moe_table_ok(x, up):
+        return native().moe_decode_up_swiglu(x, up.ptrs, topi, up.E, F_)
+    return ref.moe_decode_up_swiglu(x, up.tensors, topi).to(x.dtype)
+
+
+def moe_decode_down_add_rmsnorm(act, down: MoEExpertTable, topi, topw, residual, norm_w, eps: float):
+    """``(rmsnorm(s) * norm_w, s)`` with ``s = sum_j topw[t, j] (act[t k + j] @ W_down[topi[t, j]]^T)
+    + residual`` (``W_down[e] = [h, F]``; fixed-order combine in slot order, no atomics)."""
+    if moe_decode_ok(residual, down.E, topi.shape[1], down.shape[0], down.shape[1]) and _moe_table_ok(act, down):
+        return native().moe_decode_down_add_rmsnorm(act, down.ptrs, topi, topw, residual, norm_w, eps, down.E)
+    xn, s = ref.moe_decode_down_add_rmsnorm(act, down.tensors, topi, topw, residual, norm_w, eps)
+    return xn.to(residual.dtype), s.to(residual.dtype)
+
+
 def sample(logits, temperature, top_k, top_p, uniform):
     if use_native(logits):
         return native().sample(logits, temperature, top_k, top_p, uniform)
@@ -601,4 +675,5 @@ __all__ = [
     "sample", "decode_linear", "decode_linear_fp8", "decode_fused_ok", "decode_qkv_rope_cache", "decode_up_swiglu", "decode_attention_qkv", "up_swiglu",
     "decode_linear_add_rmsnorm", "rope_qkv_cache", "paged_prefill_attention", "prefill_work_list", "attn_merge_",
     "rms_rstd", "rowscale_ok", "linear_rowscale", "up_swiglu_rowscale", "linear_acc_",
+    "MoEExpertTable", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",
 ]

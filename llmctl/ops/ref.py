@@ -375,3 +375,62 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
         j = int(torch.searchsorted(cum, torch.tensor([r], device=cum.device, dtype=cum.dtype), right=True)[0])
         out[i] = min(j, V - 1)
     return out
+
+
+# ----------------------------------------------------------------------------- routed-expert decode MLP
+def moe_route(x: torch.Tensor, w_router: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-k routing of ``x [M, h]`` over ``w_router [E, h]``: ``(topi int32 [M, k], topw fp32 [M, k])``.
+
+    The model's definition (``MoEMLP.forward``): the logits are ``linear(x, w_router)`` -- fp32
+    accumulation rounded to the activation dtype (bf16 on the GPU) -- then softmax in fp32, the k
+    largest probabilities in descending order, weights renormalised over the picks.  On equal
+    probabilities the lowest expert index wins (a stable descending sort; ``torch.topk`` leaves the
+    tie order unspecified)."""
+    logits = (x.float() @ w_router.float().t()).to(x.dtype).float()
+    probs = logits.softmax(-1)
+    vals, idx = torch.sort(probs, dim=-1, descending=True, stable=True)
+    topw = vals[:, :k]
+    return idx[:, :k].to(torch.int32), topw / topw.sum(-1, keepdim=True)
+
+
+def moe_decode_up_swiglu(x, experts_up, topi) -> torch.Tensor:
+    """fp32 ``act [M k, F]``: row ``t k + j`` = ``silu(g) * u`` of ``x[t] @ experts_up[topi[t, j]]^T``
+    (each ``[2F, h]``, gate rows first)."""
+    M, k = topi.shape
+    F_ = experts_up[0].shape[0] // 2
+    flat = topi.reshape(-1).long()
+    xf = x.float()
+    act = torch.zeros(M * k, F_, dtype=torch.float32, device=x.device)
+    for e, w in enumerate(experts_up):
+        c = (flat == e).nonzero().flatten()
+        if c.numel():
+            gu = xf[torch.div(c, k, rounding_mode="floor")] @ w.float().t()
+            act[c] = F.silu(gu[:, :F_]) * gu[:, F_:]
+    return act
+
+
+def moe_decode_down_add_rmsnorm(act, experts_down, topi, topw, residual, norm_w, eps: float):
+    """fp32 ``(xn, res_out)``: ``res_out[t] = sum_j topw[t, j] act[t k + j] @ experts_down[topi[t, j]]^T
+    + residual[t]`` (slot order), ``xn = rmsnorm(res_out) * norm_w``."""
+    M, k = topi.shape
+    flat = topi.reshape(-1).long()
+    af = act.float()
+    d = torch.zeros(M * k, experts_down[0].shape[0], dtype=torch.float32, device=act.device)
+    for e, w in enumerate(experts_down):
+        c = (flat == e).nonzero().flatten()
+        if c.numel():
+            d[c] = af[c] @ w.float().t()
+    d = d.view(M, k, -1)
+    y = torch.zeros_like(d[:, 0])
+    for j in range(k):
+        y = y + topw[:, j].float().unsqueeze(-1) * d[:, j]
+    s = y + residual.float()
+    xn = s * torch.rsqrt(s.pow(2).mean(-1, keepdim=True) + eps) * norm_w.float()
+    return xn, s
+
+
+def moe_decode_mlp(x, experts_up, experts_down, topi, topw, residual, norm_w, eps: float):
+    """The whole routed MLP of a decode step in fp32 with no intermediate rounding: expert SwiGLU
+    MLPs of the routed copies, weighted combine, residual add and RMSNorm -> ``(xn, res_out)``."""
+    act = moe_decode_up_swiglu(x, experts_up, topi)
+    return moe_decode_down_add_rmsnorm(act, experts_down, topi, topw, residual, norm_w, eps)

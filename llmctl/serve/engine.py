@@ -128,8 +128,13 @@ class InferenceEngine:
                                                   scheduler, block_size, prefix_cache=self.prefix_cache)
         self.max_batch_size = max_batch_size
         self.rope = self.model.rope_tables(self.max_model_len, self.device)
-        # MoE routing sizes the expert segments on the host: decode runs eagerly
-        self.use_graphs = use_graphs and self.device.type == "cuda" and not cfg.is_moe
+        # MoE decode on the routed-expert kernels (ops.moe_route / moe_decode_up_swiglu /
+        # moe_decode_down_add_rmsnorm): per layer, the pointer tables of the expert weights
+        self._moe: Optional[List[Tuple[ops.MoEExpertTable, ops.MoEExpertTable]]] = self._moe_tables()
+        if self._moe is not None and self._w8 is not None:
+            log.info("engine: fp8 decode weights cover the attention projections; the experts stay bf16")
+        # the eager MoE module sizes the expert segments on the host: graphs only on the routed kernels
+        self.use_graphs = use_graphs and self.device.type == "cuda" and (not cfg.is_moe or self._fused_decode())
         self._graphs: Dict[int, Tuple[torch.cuda.CUDAGraph, Dict[str, torch.Tensor]]] = {}
         # sampling uniforms come from the host (one H2D copy with the step's other inputs), so
         # in-graph sampling and the eager path draw the same stream
@@ -156,6 +161,40 @@ class InferenceEngine:
             out.append(((layer.wqkv.float() * layer.attn_norm_w.float()).to(layer.wqkv.dtype).contiguous(),
                         (layer.w_up.float() * layer.mlp_norm_w.float()).to(layer.w_up.dtype).contiguous()))
         return out
+
+    MOE_MAX_ROWS = 64  # the routed-expert decode kernels take at most 64 token rows (ops.moe_decode_ok)
+
+    def _moe_tables(self):
+        """(up, down) ``ops.MoEExpertTable`` per layer, or None when the model's MoE MLPs do not fit
+        the routed-expert decode kernels (GPU, TP = 1, EP = 1, bf16, every layer routed, dimensions
+        within ``ops.moe_decode_ok``)."""
+        cfg = self.cfg
+        if not cfg.is_moe or self.device.type != "cuda" or self.tp != 1 or self.dtype != torch.bfloat16:
+            return None
+        probe = torch.empty(1, cfg.hidden, dtype=self.dtype, device=self.device)
+        if not ops.moe_decode_ok(probe, cfg.num_experts, cfg.experts_per_token, cfg.hidden, cfg.moe_ffn):
+            return None
+        out = []
+        for layer in self.model.layers:
+            moe = layer.moe
+            if moe is None or moe.ep != 1 or moe.w_router.dtype != torch.bfloat16 or not moe.w_router.is_contiguous():
+                return None
+            up, down = ops.MoEExpertTable(moe.experts_up), ops.MoEExpertTable(moe.experts_down)
+            if (up.dtype != torch.bfloat16 or down.dtype != torch.bfloat16 or up.E != cfg.num_experts
+                    or up.shape != (2 * cfg.moe_ffn, cfg.hidden) or down.shape != (cfg.hidden, cfg.moe_ffn)):
+                return None
+            out.append((up, down))
+        return out
+
+    def _moe_fused(self, n: int = 1) -> bool:
+        """MoE MLPs of an ``n``-row decode step on the routed-expert kernels (knob
+        ``moe_decode_fused`` off: the eager ``MoEMLP`` module, A/B)."""
+        return self._moe is not None and self.knobs.moe_decode_fused and n <= self.MOE_MAX_ROWS
+
+    def _graph_ok(self, n: int) -> bool:
+        """Does an ``n``-row decode step replay a captured graph?  (MoE: buckets above the routed
+        kernels' row limit run eagerly through the ``MoEMLP`` module, which syncs with the host.)"""
+        return self.use_graphs and (not self.cfg.is_moe or self._moe_fused(self._bucket(n)))
 
     def _norm_fold_ok(self, T: int) -> bool:
         return self._nf is not None and self.knobs.prefill_norm_fold and T > 0 and T % 256 == 0
@@ -416,22 +455,24 @@ class InferenceEngine:
         return self.knobs.mixed_steps
 
     # ------------------------------------------------------------------ decode
-    def _fused_decode(self) -> bool:
+    def _fused_decode(self, n: int = 1) -> bool:
         """Decode layers on the fused-epilogue projections (``ops.decode_qkv_rope_cache`` /
         ``decode_up_swiglu`` / ``decode_linear_add_rmsnorm``): 10 kernels per layer instead of 13
         (the RoPE/cache-write, SwiGLU and add+RMSNorm passes ride on the projections' finalize).  Needs the GPU path,
         RMSNorm, RoPE and a gated MLP; at TP > 1 the row-parallel projections' all-reduce, bias,
         residual add and next RMSNorm are one custom-all-reduce kernel
-        (``_reduce_add_rmsnorm``); knob ``decode_fused`` off keeps the unfused layer (A/B)."""
+        (``_reduce_add_rmsnorm``); knob ``decode_fused`` off keeps the unfused layer (A/B).
+        MoE models: the MLP half is route -> routed gate/up + SwiGLU -> routed down + combine +
+        residual + RMSNorm (``_moe_fused``), for steps of at most ``MOE_MAX_ROWS`` rows."""
         cfg, m = self.cfg, self.model
         return (self.device.type == "cuda" and (self.tp == 1 or self._fused_reduce_ok()) and self.rope is not None
                 and cfg.gated_mlp
-                and not cfg.is_moe and m.final_norm_b is None
+                and (not cfg.is_moe or self._moe_fused(n)) and m.final_norm_b is None
                 and all(l.attn_norm_b is None and l.mlp_norm_b is None for l in m.layers)
                 and self.knobs.decode_fused)
 
     def _decode_body(self, ids, positions, slots, block_tables, ctx_lens) -> torch.Tensor:
-        if self._fused_decode():
+        if self._fused_decode(ids.shape[0]):
             return self._decode_body_fused(ids, positions, slots, block_tables, ctx_lens)
         x = self._embed(ids, positions)
         res = None
@@ -508,8 +549,14 @@ class InferenceEngine:
             else:
                 xn, res = ops.decode_linear_add_rmsnorm(o.view(o.shape[0], -1), wo, layer.bo, res,
                                                         layer.mlp_norm_w, eps, w_scale=so)
-            act = ops.decode_up_swiglu(xn, wu, layer.b_up, w_scale=su)  # the local F shard
             nw = layers[li + 1].attn_norm_w if li + 1 < len(layers) else m.final_norm_w
+            if layer.moe is not None:  # routed experts: all routing stays on the device
+                up_t, down_t = self._moe[li]
+                topi, topw = ops.moe_route(xn, layer.moe.w_router, layer.moe.k)
+                act = ops.moe_decode_up_swiglu(xn, up_t, topi)
+                xn, res = ops.moe_decode_down_add_rmsnorm(act, down_t, topi, topw, res, nw, eps)
+                continue
+            act = ops.decode_up_swiglu(xn, wu, layer.b_up, w_scale=su)  # the local F shard
             if tp:
                 xn, res = self._reduce_add_rmsnorm(lin(act, wd, sd), layer.b_down, res, nw, eps)
             else:
@@ -605,6 +652,7 @@ class InferenceEngine:
         self.kv_cache = None
         self._w8 = self._w8_head = None
         self._nf = None
+        self._moe = None
         self.rope = None
         if self.device.type == "cuda":
             torch.cuda.empty_cache()
@@ -630,7 +678,7 @@ class InferenceEngine:
         ids, positions, slots, ctx, bt = plan["ids"], plan["positions"], plan["slots"], plan["ctx"], plan["bt"]
         n = len(ids)
         self.stats["decode_tokens"] += n
-        if self.use_graphs:
+        if self._graph_ok(n):
             g, b = self._stage_and_replay(plan, cont=False)
             return b["logits"][:n]
         d = self.device
@@ -714,7 +762,7 @@ class InferenceEngine:
             plan.setdefault("ids", np.zeros(n, dtype=np.int64))
         toks = self._decode_sample_exec(self._publish(plan))
         d = self.device
-        if self.use_graphs:
+        if self._graph_ok(n):
             b = self._graphs[self._bucket(n)][1]
             out = b["host_toks"][b["tflip"]]
             b["tflip"] ^= 1
@@ -734,7 +782,7 @@ class InferenceEngine:
         buffer, all bucket rows)."""
         use_knobs(self.knobs)
         cont = bool(plan["cont"])
-        if self.use_graphs:
+        if self._graph_ok(len(plan["positions"])):
             _, b = self._stage_and_replay(plan, cont)
             return b["toks"]
         d = self.device
