@@ -51,7 +51,7 @@ def e2e(
     max_batch_tokens: Optional[int] = typer.Option(None, help="Prefill token budget per step (default: 4096 "
                                                                  "for prefill_first, 8192 otherwise)"),
     kv_cache_dtype: str = typer.Option("auto", help="KV cache element: auto (model dtype) | fp8 (e4m3fn)"),
-    weight_dtype: str = typer.Option("auto", help="Decode projection weights: auto (model dtype) | fp8 (e4m3fn, row scales)"),
+    weight_dtype: str = typer.Option("auto", help="Decode projection weights: auto (model dtype) | fp8 (e4m3fn, row scales) | int4 (group-128 scales)"),
 ) -> None:
     """End-to-end serving benchmark (TTFT p50/p99, TPOT, tokens/s).
 

@@ -5,6 +5,8 @@ Formats: ``safetensors`` (consolidated, layout-independent llmctl names), ``hf``
 ``tensorrt`` / ``gguf`` are reported as unsupported on this platform (exit code 2).
 Quantizers (plugin group ``quantizers``): ``int8`` (per-output-channel absmax RTN) and
 ``fp8`` (OCP e4m3, per-channel scale — the gfx950 MFMA fp8 format); the reference's names
+``int4-g128`` is the group-scaled int4 the serving engine's ``--weight-dtype int4`` decodes from (one
+fp32 scale per output row and 128 input features; needs in_features % 128 == 0).  The reference's names
 ``int8-awq`` / ``int4-gptq`` map to RTN int8 / int4 with a warning (no calibration data).
 """
 
@@ -25,7 +27,7 @@ app = typer.Typer(help="Export models to deployment formats")
 def convert(
     ckpt: str = typer.Option(..., help="Checkpoint directory"),
     format: str = typer.Option("safetensors", help="safetensors | hf | onnx | tensorrt | gguf"),
-    quant: Optional[str] = typer.Option(None, help="int8 | fp8 | int4 | int8-awq | int4-gptq"),
+    quant: Optional[str] = typer.Option(None, help="int8 | fp8 | int4 | int4-g128 | int8-awq | int4-gptq"),
     out: Path = typer.Option(..., help="Output directory"),
 ) -> None:
     """Convert a checkpoint to a deployment format."""

@@ -33,8 +33,9 @@ def start(
     cuda_graphs: bool = typer.Option(True, "--hip-graphs/--no-hip-graphs", help="Capture decode steps in hipGraphs"),
     tensor_parallel: int = typer.Option(1, help="TP degree (run under torchrun for >1)"),
     kv_cache_dtype: str = typer.Option("auto", help="KV cache element: auto (the model dtype) or fp8 (OCP e4m3fn)"),
-    weight_dtype: str = typer.Option("auto", help="Decode projection weights: auto (the model dtype) or fp8 (OCP "
-                                                  "e4m3fn, per-row scales; prefill keeps the model dtype)"),
+    weight_dtype: str = typer.Option("auto", help="Decode projection weights: auto (the model dtype), fp8 (OCP "
+                                                  "e4m3fn, per-row scales) or int4 (group-128 scales, W4A16); "
+                                                  "prefill keeps the model dtype"),
 ) -> None:
     """Start the inference server."""
     from llmctl.serve.server import create_inference_server

@@ -16,6 +16,7 @@ from .functional import (
     decode_fused_ok,
     decode_linear,
     decode_linear_fp8,
+    decode_linear_int4,
     decode_linear_add_rmsnorm,
     decode_qkv_rope_cache,
     decode_up_swiglu,
@@ -49,7 +50,7 @@ from .functional import (
 
 __all__ = [
     "ref", "native_available", "adamw_step_", "add_layernorm", "add_rmsnorm", "cross_entropy", "decode_linear",
-    "decode_attention_qkv", "decode_fused_ok", "decode_linear_add_rmsnorm", "decode_qkv_rope_cache", "decode_up_swiglu",
+    "decode_linear_fp8", "decode_linear_int4", "decode_attention_qkv", "decode_fused_ok", "decode_linear_add_rmsnorm", "decode_qkv_rope_cache", "decode_up_swiglu",
     "flash_attention", "gelu", "kv_cache_write", "l2norm_sq", "layernorm", "paged_attention_decode",
     "paged_prefill_attention", "prefill_work_list", "attn_merge_",
     "rmsnorm", "rope_qkv", "rope_flash_attention", "rope_qkv_cache", "sample", "swiglu", "transpose_", "up_swiglu",

@@ -54,6 +54,7 @@ TORCH_LIBRARY(llmctl, m) {
   m.def("decode_linear_partials(Tensor x, Tensor w, Tensor? w_scale=None) -> Tensor");
   m.def("decode_linear_add_rmsnorm(Tensor x, Tensor w, Tensor? bias, Tensor residual, Tensor norm_w, float eps, Tensor? w_scale=None) -> (Tensor, Tensor)");
   m.def("decode_linear_fp8(Tensor x, Tensor w, Tensor w_scale, Tensor? bias) -> Tensor");
+  m.def("decode_linear_int4(Tensor x, Tensor qweight, Tensor scale, Tensor? bias) -> Tensor");
   // routed-expert decode MLP (moe_decode.hip); *_ptrs: int64 [E] device table of expert weight pointers
   m.def("moe_route(Tensor x, Tensor w_router, int k) -> (Tensor, Tensor)");
   m.def("moe_decode_up_swiglu(Tensor x, Tensor up_ptrs, Tensor topi, int E, int F) -> Tensor");

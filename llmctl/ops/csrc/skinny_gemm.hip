@@ -353,6 +353,129 @@ __global__ __launch_bounds__(256) void decode_gemm_w8_kernel(const unsigned shor
   *reinterpret_cast<f32x4_t*>(ws + ((long)blockIdx.y * M + r) * N + n) = acc;
 }
 
+// int4 weights, one fp32 scale per output row and group of 128 input features (W4A16, decode only;
+// llmctl.plugins.quantizers.quantize_int4_g128): u = q + 8 in a nibble, byte j of a row = k 2j (low)
+// and 2j + 1 (high), so the weight stream is a quarter of the bf16 one (+ 4 B of scale per 64 B).
+//   * a lane's 16-B load holds 32 consecutive k of its row (k = 32 g + [0, 32) of a 128-deep block): the
+//     A operands of the block's 4 MFMA steps, one dword (8 nibbles) each; a wave-instruction covers 64
+//     contiguous bytes of each of its 16 rows, one load per lane and block;
+//   * unpack, 7 VALU ops per 8 weights: ((d >> 4 t) & 0x000F000F) | 0x43004300 is the bf16 pair
+//     (128 + u[t], 128 + u[t + 4]) exactly, so MFMA step s of lane group g reads k = 32 g + 8 s +
+//     {0, 4, 1, 5, 2, 6, 3, 7}; the token rows are staged in LDS in that order (and lane-group-major,
+//     g at a multiple of 256 B: the ds_read_b128 of a 16-lane group then hits 16 distinct 16-B slots);
+//   * a K block is one scale group: its 4 MFMAs run on exact small integers into a fresh fp32 tile
+//     t = sum_k (136 + q) x, and acc += scale[row][group] * (t - 136 sum_k x); the per-token group sums
+//     of x are taken once while staging, the scales of the workgroup's 64 rows x NB groups go through
+//     LDS.  No per-weight multiply, 8 VALU ops per lane and block for the scaling.
+//   * NT 16-row tiles per wave (64 NT weight rows per workgroup): the staged token rows of a chunk are
+//     as many bytes as 64 int4 weight rows, two tiles share them (and each B operand read from LDS).
+// The partials and the finalize passes are the bf16 path's.
+__device__ __forceinline__ bf16x8_t u4x8_to_bf16x8(unsigned d, unsigned mask, unsigned one28) {
+  bf16x8_t r;
+  unsigned* w = reinterpret_cast<unsigned*>(&r);
+#pragma unroll
+  for (int t = 0; t < 4; ++t) w[t] = ((d >> (4 * t)) & mask) | one28;
+  return r;
+}
+
+template <int NB, int NT>
+__global__ __launch_bounds__(256) void decode_gemm_w4_kernel(const unsigned short* __restrict__ x,
+                                                             const unsigned char* __restrict__ w,
+                                                             const float* __restrict__ wscale,
+                                                             float* __restrict__ ws, int M, int N, int K) {
+  static_assert(NB % 4 == 0, "xsum rows are read as float4");
+  constexpr int KC = NB * KBLK, XST = KC + 8, GS = KC / 4;  // GS: lane group stride within an LDS row
+  constexpr int WR = 64 * NT;                               // weight rows per workgroup: NT 16-row tiles per wave
+  __shared__ __attribute__((aligned(16))) unsigned short xs[16 * XST];
+  __shared__ __attribute__((aligned(16))) float xsum[16][NB];  // sum of x over [token][K block]
+  __shared__ __attribute__((aligned(16))) float ssc[WR][NB];   // scale of [weight row][K block]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * WR + wave * 16 * NT;
+  const int kc0 = blockIdx.y * KC;
+  const int kc = min(KC, K - kc0);
+  const int nb = kc / KBLK;
+  uint4 a[NT][NB];
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    const unsigned char* wrow = w + (long)(n0 + 16 * i + r) * (K >> 1) + (kc0 >> 1) + 16 * g;
+#pragma unroll
+    for (int u = 0; u < NB; ++u)
+      a[i][u] = *reinterpret_cast<const uint4*>(wrow + (u < nb ? u : nb - 1) * (KBLK / 2));
+  }
+  // thread -> NB / 4 scales of weight rows tid / 4 + 64 i (past-the-end blocks re-read the last one)
+  const float* srow = wscale + (long)(blockIdx.x * WR + (tid >> 2)) * (K / KBLK) + kc0 / KBLK;
+  float sv[NT][NB / 4];
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+#pragma unroll
+    for (int e = 0; e < NB / 4; ++e) {
+      const int u = (tid & 3) * (NB / 4) + e;
+      sv[i][e] = srow[(long)64 * i * (K / KBLK) + (u < nb ? u : nb - 1)];
+    }
+  __builtin_amdgcn_sched_barrier(0);
+  // token rows of the chunk -> LDS (rows >= M as zeros): 16 consecutive threads = one (token, K block)
+  const int c8 = kc >> 3;
+  for (int i = tid; i < 16 * c8; i += 256) {  // 16 c8 % 256 == 0: the whole workgroup takes every trip
+    const int m = i / c8, c = i - m * c8;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (m < M) v = *reinterpret_cast<const uint4*>(x + (long)m * K + kc0 + c * 8);
+    float s = 0.f;
+    const unsigned vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s += __uint_as_float(vv[j] << 16) + __uint_as_float(vv[j] & 0xFFFF0000u);
+    uint4 p;  // elements (0, 4, 1, 5, 2, 6, 3, 7)
+    p.x = (v.x & 0xFFFFu) | (v.z << 16);
+    p.y = (v.x >> 16) | (v.z & 0xFFFF0000u);
+    p.z = (v.y & 0xFFFFu) | (v.w << 16);
+    p.w = (v.y >> 16) | (v.w & 0xFFFF0000u);
+    const int u = c >> 4, cg = (c >> 2) & 3, cs = c & 3;
+    *reinterpret_cast<uint4*>(xs + m * XST + cg * GS + u * 32 + cs * 8) = p;
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) s += __shfl_xor(s, o);
+    if ((tid & 15) == 0) xsum[m][u] = s;
+  }
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+#pragma unroll
+    for (int e = 0; e < NB / 4; ++e) ssc[64 * i + (tid >> 2)][(tid & 3) * (NB / 4) + e] = sv[i][e];
+  __syncthreads();
+  const unsigned short* xrow = xs + r * XST + g * GS;
+  float xsv[NB];
+#pragma unroll
+  for (int u = 0; u < NB; u += 4) *reinterpret_cast<float4*>(xsv + u) = *reinterpret_cast<const float4*>(&xsum[r][u]);
+  f32x4_t acc[NT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i) acc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  // the two unpack constants held in VGPRs (opaque to the optimiser): (d & mask) | c is then one
+  // v_and_or_b32; as literals it is a v_and + a v_or (a VOP3 takes no literal)
+  unsigned mask = 0x000F000Fu, one28 = 0x43004300u;
+  asm volatile("" : "+v"(mask), "+v"(one28));
+#pragma unroll
+  for (int u = 0; u < NB; ++u) {
+    if (u < nb) {
+      bf16x8_t xb[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) xb[s] = *reinterpret_cast<const bf16x8_t*>(xrow + u * 32 + 8 * s);
+      const float off = -136.f * xsv[u];
+#pragma unroll
+      for (int i = 0; i < NT; ++i) {
+        const unsigned q[4] = {a[i][u].x, a[i][u].y, a[i][u].z, a[i][u].w};
+        f32x4_t t = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) t = mfma16(u4x8_to_bf16x8(q[s], mask, one28), xb[s], t);
+        // D: lane holds [weight row n0 + 16 i + 4 g + j][token r]
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] += ssc[wave * 16 * NT + 16 * i + 4 * g + j][u] * (t[j] + off);
+      }
+    }
+  }
+  if (r >= M) return;
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+    *reinterpret_cast<f32x4_t*>(ws + ((long)blockIdx.y * M + r) * N + n0 + 16 * i + 4 * g) = acc[i];
+}
+
 // y[m][n] = bf16(sum_s ws[s][m][n] + bias[n]), 4 columns per thread
 __global__ __launch_bounds__(256) void decode_finalize_kernel(const float* __restrict__ ws,
                                                               const unsigned short* __restrict__ bias,
@@ -649,10 +772,12 @@ void check_decode_operands(const at::Tensor& x, const at::Tensor& w, const c10::
                            const char* who) {
   LLMCTL_CHECK(x.dim() == 2 && w.dim() == 2 && x.is_contiguous() && w.is_contiguous(), who, ": 2-D contiguous");
   LLMCTL_CHECK(x.is_cuda() && w.is_cuda() && x.scalar_type() == at::kBFloat16 &&
-                   (w.scalar_type() == at::kBFloat16 || w.scalar_type() == at::kFloat8_e4m3fn),
-               who, ": bf16 GPU activations, bf16 or fp8 (e4m3fn) weights");
+                   (w.scalar_type() == at::kBFloat16 || w.scalar_type() == at::kFloat8_e4m3fn ||
+                    w.scalar_type() == at::kByte),
+               who, ": bf16 GPU activations, bf16, fp8 (e4m3fn) or packed int4 (uint8) weights");
   const int M = x.size(0), K = x.size(1), N = w.size(0);
-  LLMCTL_CHECK(w.size(1) == K && M >= 1 && M <= 16 && N % 64 == 0 && K % KBLK == 0, who,
+  // int4: two k per byte, w [N, K / 2]
+  LLMCTL_CHECK(w.size(1) * (w.scalar_type() == at::kByte ? 2 : 1) == K && M >= 1 && M <= 16 && N % 64 == 0 && K % KBLK == 0, who,
                ": needs M <= 16, N % 64 == 0, K % 128 == 0 (got ", M, "x", N, "x", K, ")");
   if (bias.has_value() && bias->defined())
     LLMCTL_CHECK(bias->scalar_type() == at::kBFloat16 && bias->is_contiguous() && bias->numel() == N, who,
@@ -664,8 +789,10 @@ const unsigned short* bias_ptr(const c10::optional<at::Tensor>& bias) {
 }
 
 bool w_fp8(const at::Tensor& w) { return w.scalar_type() == at::kFloat8_e4m3fn; }
+bool w_int4(const at::Tensor& w) { return w.scalar_type() == at::kByte; }
 
-// x W^T as fp32 K-chunk partials ws [KS][M][N]; returns KS.  fp8 W: w_scale [N] fp32 row scales.
+// x W^T as fp32 K-chunk partials ws [KS][M][N]; returns KS.  fp8 W: w_scale [N] fp32 row scales;
+// int4 W (uint8 [N, K / 2]): w_scale [N, K / 128] fp32 group scales.
 int decode_partials(const at::Tensor& x, const at::Tensor& w, at::Tensor& ws,
                     const c10::optional<at::Tensor>& w_scale = c10::nullopt) {
   const int M = x.size(0), K = x.size(1), N = w.size(0);
@@ -682,6 +809,24 @@ int decode_partials(const at::Tensor& x, const at::Tensor& w, at::Tensor& ws,
                        (size_t)16 * (kFusedKC + 8) * 2, stream(), bf_ptr(x),
                        static_cast<const unsigned char*>(w.data_ptr()), w_scale->data_ptr<float>(),
                        ws.data_ptr<float>(), M, N, K);
+  } else if (w_int4(w)) {
+    LLMCTL_CHECK(w_scale.has_value() && w_scale->defined() && w_scale->scalar_type() == at::kFloat &&
+                     w_scale->is_contiguous() && w_scale->dim() == 2 && w_scale->size(0) == N &&
+                     w_scale->size(1) == K / KBLK && w_scale->is_cuda(),
+                 "int4 decode weights need fp32 group scales [N, K / 128] on the GPU");
+    const unsigned char* wp = w.data_ptr<unsigned char>();
+    // one 16-row tile per wave, or two (128 weight rows per workgroup share the staged token rows, which
+    // are as many bytes as 64 int4 rows) on the wide projections: at 16 tokens two tiles measured 23.6 vs
+    // 25.9 us on the GPT-7B gate/up (N = 22016) and 28.9 vs 31.0 on the LM head, but 18.0 vs 16.2 on QKV
+    // (N = 12288), 19.6 vs 18.0 on down and 13.1 vs 11.4 on o, and 5.55 vs 5.47 ms per decode step when
+    // taken everywhere (profiles/decode_w4.txt).  Knob decode_w4_nt = 1 / 2 forces one (A/B).
+    const int nt = (int)knob("decode_w4_nt", 0);
+    if (N % 128 == 0 && (nt == 2 || (nt == 0 && N >= 16384)))
+      hipLaunchKernelGGL((decode_gemm_w4_kernel<kFusedKC / KBLK, 2>), dim3(N / 128, KS), dim3(256), 0, stream(),
+                         bf_ptr(x), wp, w_scale->data_ptr<float>(), ws.data_ptr<float>(), M, N, K);
+    else
+      hipLaunchKernelGGL((decode_gemm_w4_kernel<kFusedKC / KBLK, 1>), dim3(N / 64, KS), dim3(256), 0, stream(),
+                         bf_ptr(x), wp, w_scale->data_ptr<float>(), ws.data_ptr<float>(), M, N, K);
   } else if (decode_v3())  // (its LDS row stride is the full chunk's, whatever K is)
     launch_pre(bf_ptr(x), bf_ptr(w), nullptr, nullptr, ws.data_ptr<float>(), M, N, K, KS);
   else
@@ -790,8 +935,25 @@ at::Tensor decode_linear_fp8(const at::Tensor& x, const at::Tensor& w, const at:
   return y;
 }
 
+// y [M, N] = x W^T (+ b) with int4 W (uint8 [N, K / 2], two k per byte) and fp32 group-128 scales [N, K / 128]
+at::Tensor decode_linear_int4(const at::Tensor& x, const at::Tensor& w, const at::Tensor& w_scale,
+                              const c10::optional<at::Tensor>& bias) {
+  check_decode_operands(x, w, bias, "decode_linear_int4");
+  LLMCTL_CHECK(w_int4(w), "decode_linear_int4: packed int4 (uint8) weights");
+  const int M = x.size(0), N = w.size(0);
+  const c10::DeviceGuard guard(x.device());
+  at::Tensor ws;
+  const int KS = decode_partials(x, w, ws, w_scale);
+  auto y = at::empty({M, N}, x.options());
+  const long n4 = (long)M * N / 4;
+  hipLaunchKernelGGL(decode_finalize_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream(),
+                     ws.data_ptr<float>(), bias_ptr(bias), bf_mut(y), M, N, KS);
+  return y;
+}
+
 TORCH_LIBRARY_IMPL(llmctl, CUDA, m) {
   m.impl("decode_linear_fp8", &decode_linear_fp8);
+  m.impl("decode_linear_int4", &decode_linear_int4);
   m.impl("skinny_linear", &skinny_linear);
   m.impl("skinny_linear_cfg", &skinny_linear_cfg);
   m.impl("decode_qkv_rope_cache", &decode_qkv_rope_cache);

@@ -448,8 +448,13 @@ def decode_linear(x, w, b=None):
 
 
 def _dequant(w, w_scale, dtype):
-    """bf16 image of an fp8 (e4m3fn) weight with fp32 row scales (fallback paths)."""
-    return w if w_scale is None else (w.float() * w_scale.float().unsqueeze(1)).to(dtype)
+    """bf16 image of an fp8 (e4m3fn) weight with fp32 row scales, or of a packed int4 (uint8) weight
+    with fp32 group-128 scales (fallback paths)."""
+    if w_scale is None:
+        return w
+    if w.dtype == torch.uint8:
+        return ref.dequant_int4_g128(w, w_scale).to(dtype)
+    return (w.float() * w_scale.float().unsqueeze(1)).to(dtype)
 
 
 def decode_linear_fp8(x, w, w_scale, b=None):
@@ -461,14 +466,24 @@ def decode_linear_fp8(x, w, w_scale, b=None):
     return decode_linear(x, _dequant(w, w_scale, x.dtype), b)
 
 
+def decode_linear_int4(x, qweight, scale, b=None):
+    """``x @ dequant(qweight, scale)^T (+ b)`` for decode-shaped inputs with group-128 int4 weights
+    (W4A16, ``quantizers.quantize_int4_g128``: uint8 ``[N, K/2]`` + fp32 scales ``[N, K/128]``;
+    ``csrc/skinny_gemm.hip``'s int4 weight stream, 4.25 bits per weight)."""
+    if decode_fused_ok(x, qweight):
+        return native().decode_linear_int4(x, qweight, scale, b)
+    return decode_linear(x, _dequant(qweight, scale, x.dtype), b)
+
+
 def decode_fused_ok(x, w) -> bool:
     """Can this decode projection run with a fused epilogue (``csrc/skinny_gemm.hip``: the v2
     weight-streaming GEMM's K-chunk partials summed by a finalize pass that also applies RoPE +
-    paged-cache write, SwiGLU or residual + RMSNorm)?  <= 16 tokens, bf16, out features a
-    multiple of 64, in features of 128.  Knob ``decode_fused`` off disables (A/B)."""
+    paged-cache write, SwiGLU or residual + RMSNorm)?  <= 16 tokens, bf16 activations, bf16 / fp8
+    (e4m3fn) / packed int4 (uint8 ``[N, K/2]``) weights, out features a multiple of 64, in features
+    of 128.  Knob ``decode_fused`` off disables (A/B)."""
     return (knobs().decode_fused and use_native(x) and x.dim() == 2
             and 1 <= x.shape[0] <= 16 and x.dtype == torch.bfloat16
-            and w.dtype in (torch.bfloat16, torch.float8_e4m3fn) and x.is_contiguous()
+            and w.dtype in (torch.bfloat16, torch.float8_e4m3fn, torch.uint8) and x.is_contiguous()
             and w.is_contiguous() and w.shape[0] % 64 == 0 and x.shape[1] % 128 == 0)
 
 
@@ -476,7 +491,8 @@ def decode_qkv_rope_cache(x, w, b, cos, sin, nq: int, nkv: int, positions, k_cac
                           w_scale=None):
     """Decode QKV projection + RoPE + paged-cache write of K/V in one finalize pass; returns
     ``q [T, nq, D]``.  Same result as ``rope_qkv_cache(decode_linear(x, w, b), ...)[0]``.
-    ``w_scale``: fp32 row scales of an fp8 (e4m3fn) ``w``."""
+    ``w_scale``: fp32 row scales of an fp8 (e4m3fn) ``w``, or fp32 group-128 scales of a packed
+    int4 one."""
     if decode_fused_ok(x, w):
         return native().decode_qkv_rope_cache(x, w, b, cos, sin, nq, nkv, positions.to(torch.int32).contiguous(),
                                               k_cache, v_cache, slots, w_scale)
@@ -672,7 +688,7 @@ __all__ = [
     "rmsnorm", "add_rmsnorm", "layernorm", "add_layernorm", "rope_qkv", "flash_attention", "rope_flash_attention",
     "swiglu",
     "gelu", "cross_entropy", "adamw_step_", "l2norm_sq", "kv_cache_write", "paged_attention_decode",
-    "sample", "decode_linear", "decode_linear_fp8", "decode_fused_ok", "decode_qkv_rope_cache", "decode_up_swiglu", "decode_attention_qkv", "up_swiglu",
+    "sample", "decode_linear", "decode_linear_fp8", "decode_linear_int4", "decode_fused_ok", "decode_qkv_rope_cache", "decode_up_swiglu", "decode_attention_qkv", "up_swiglu",
     "decode_linear_add_rmsnorm", "rope_qkv_cache", "paged_prefill_attention", "prefill_work_list", "attn_merge_",
     "rms_rstd", "rowscale_ok", "linear_rowscale", "up_swiglu_rowscale", "linear_acc_",
     "MoEExpertTable", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",

@@ -377,6 +377,26 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
     return out
 
 
+# ----------------------------------------------------------------------------- int4 decode weights
+def dequant_int4_g128(qweight: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """fp32 ``[N, K]`` image of a group-128 int4 weight (``quantizers.quantize_int4_g128``):
+    ``qweight`` uint8 ``[N, K/2]``, byte ``j`` = ``u[2j] | u[2j+1] << 4`` with ``u = q + 8`` in
+    0..15; ``scale`` fp32 ``[N, K/128]``; ``w[n, k] = (u[n, k] - 8) * scale[n, k // 128]``."""
+    N, K = qweight.shape[0], qweight.shape[1] * 2
+    if qweight.dtype != torch.uint8 or K % 128 or tuple(scale.shape) != (N, K // 128):
+        raise ValueError(f"dequant_int4_g128: need uint8 [N, K/2] and scales [N, K/128], got "
+                         f"{qweight.dtype} {tuple(qweight.shape)} and {tuple(scale.shape)}")
+    p = qweight.to(torch.int16)
+    u = torch.stack([p & 0xF, p >> 4], dim=2).reshape(N, K)
+    return (u - 8).float() * scale.float().repeat_interleave(128, dim=1)
+
+
+def decode_linear_int4(x, qweight, scale, b=None) -> torch.Tensor:
+    """fp32 ``x @ dequant(W)^T (+ b)``: the spec of the int4 decode projection."""
+    y = x.float() @ dequant_int4_g128(qweight, scale).t()
+    return y if b is None else y + b.float()
+
+
 # ----------------------------------------------------------------------------- routed-expert decode MLP
 def moe_route(x: torch.Tensor, w_router: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-k routing of ``x [M, h]`` over ``w_router [E, h]``: ``(topi int32 [M, k], topw fp32 [M, k])``.

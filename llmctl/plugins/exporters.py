@@ -116,7 +116,8 @@ def export_checkpoint(ckpt: str, fmt: str, out: str, quant: Optional[str] = None
             else:
                 qsd[k] = v
         sd = qsd
-        qinfo = {"method": "rtn", "format": name, "requested": quant, "granularity": "per-output-channel"}
+        qinfo = {"method": "rtn", "format": name, "requested": quant,
+                 "granularity": "per-output-channel, group-128" if name == "int4-g128" else "per-output-channel"}
     outp = Path(out)
     outp.mkdir(parents=True, exist_ok=True)
     save_file(sd, str(outp / "model.safetensors"), metadata={"format": "pt", "llmctl_export": fmt})

@@ -2,6 +2,9 @@
 
 * ``int8``  — symmetric per-output-channel absmax round-to-nearest (int8 + fp32 scales);
 * ``int4``  — the same at 4 bits, two values packed per byte;
+* ``int4-g128`` — 4 bits with one fp32 scale per output row and group of 128 input features,
+  offset-binary nibbles (4.25 bits per weight): the format the int4 decode kernel serves from
+  (``InferenceEngine(weight_dtype="int4")``, ``llmctl/ops/csrc/skinny_gemm.hip``);
 * ``fp8``   — OCP e4m3 (``torch.float8_e4m3fn``, the gfx950 MFMA fp8 format — NOT the
   MI300 ``fnuz`` variant) with per-channel fp32 scales.
 The reference's names ``int8-awq`` / ``int4-gptq`` are accepted as aliases of RTN int8 /
@@ -38,6 +41,20 @@ def quantize_int4(w: torch.Tensor) -> Dict[str, torch.Tensor]:
     return {"qweight": lo | (hi << 4), "scale": s.squeeze(1)}
 
 
+def quantize_int4_g128(w: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """Symmetric round-to-nearest int4, group 128 along the input features: ``scale[n, g] =
+    max|w[n, 128g : 128g + 128]| / 7`` (fp32, >= 1e-12), ``q = clamp(round(w / scale), -8, 7)``
+    stored as ``u = q + 8``; ``qweight`` uint8 ``[N, K/2]``, byte ``j`` of a row = ``u[2j]`` (low
+    nibble) ``| u[2j + 1] << 4``; ``scale`` fp32 ``[N, K/128]``."""
+    if w.dim() != 2 or w.shape[1] % 128:
+        raise ValueError(f"int4-g128 needs a 2-D weight with in_features % 128 == 0, got {tuple(w.shape)}")
+    N, K = w.shape
+    wg = w.float().reshape(N, K // 128, 128)
+    s = wg.abs().amax(dim=2, keepdim=True).clamp_min(1e-12) / 7.0
+    u = (torch.clamp(torch.round(wg / s), -8, 7) + 8).to(torch.uint8).reshape(N, K)
+    return {"qweight": (u[:, 0::2] | (u[:, 1::2] << 4)).contiguous(), "scale": s.squeeze(2).contiguous()}
+
+
 def quantize_fp8(w: torch.Tensor) -> Dict[str, torch.Tensor]:
     fmax = 448.0  # e4m3fn max
     s = _per_channel_absmax(w) / fmax
@@ -47,6 +64,10 @@ def quantize_fp8(w: torch.Tensor) -> Dict[str, torch.Tensor]:
 
 def dequantize(name: str, t: Dict[str, torch.Tensor], shape: Tuple[int, int]) -> torch.Tensor:
     name = ALIASES.get(name, name)
+    if name == "int4-g128":
+        from llmctl.ops.ref import dequant_int4_g128
+
+        return dequant_int4_g128(t["qweight"], t["scale"])
     s = t["scale"].float().unsqueeze(1)
     if name == "int8":
         return t["qweight"].float() * s
@@ -63,7 +84,8 @@ def dequantize(name: str, t: Dict[str, torch.Tensor], shape: Tuple[int, int]) ->
     raise KeyError(name)
 
 
-QUANTIZERS = {"int8": quantize_int8, "int4": quantize_int4, "fp8": quantize_fp8}
+QUANTIZERS = {"int8": quantize_int8, "int4": quantize_int4, "fp8": quantize_fp8,
+              "int4-g128": quantize_int4_g128}
 
 
 def register(reg) -> None:

@@ -84,17 +84,22 @@ class InferenceEngine:
         self.max_model_len = max_model_len or cfg.max_position_embeddings
         self.block_size = block_size
         self.max_blocks_per_seq = (self.max_model_len + block_size - 1) // block_size
-        # decode projection weights: the model's ("auto"), or an fp8 (OCP e4m3fn) copy with fp32 row
-        # scales ("fp8", W8A16) that the fused decode path streams instead (half the bytes of the
-        # HBM-bound decode GEMMs); prefill keeps the bf16 weights.  Made before the KV cache is sized.
-        self._w8: Optional[List[Dict[str, Tuple[torch.Tensor, torch.Tensor]]]] = None
-        self._w8_head: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+        # decode projection weights: the model's ("auto"), or a quantised copy that the fused decode
+        # path streams instead (the decode GEMMs are HBM-bound): "fp8" = OCP e4m3fn with fp32 row
+        # scales (W8A16, half the bytes), "int4" = group-128 int4 with fp32 group scales (W4A16, 4.25
+        # bits per weight).  Prefill keeps the bf16 weights.  Made before the KV cache is sized.
+        self._wq: Optional[List[Dict[str, Tuple[torch.Tensor, torch.Tensor]]]] = None
+        self._wq_head: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+        self._wq_kind: Optional[str] = None
         if weight_dtype in ("fp8", "fp8_e4m3", "float8_e4m3fn"):
-            if self.device.type == "cuda":
-                self._w8 = self._quantize_decode_weights()
+            self._wq_kind = "fp8"
+        elif weight_dtype in ("int4", "int4-g128", "w4a16"):
+            self._wq_kind = "int4"
         elif weight_dtype not in ("auto", "model", "bf16", "bfloat16"):
-            raise ValueError(f"weight_dtype must be auto / bf16 / fp8, got {weight_dtype!r}")
-        self.weight_dtype = "fp8" if self._w8 is not None else "auto"
+            raise ValueError(f"weight_dtype must be auto / bf16 / fp8 / int4, got {weight_dtype!r}")
+        if self._wq_kind is not None and self.device.type == "cuda":
+            self._wq = self._quantize_decode_weights(self._wq_kind)
+        self.weight_dtype = self._wq_kind if self._wq is not None else "auto"
         # prefill with the RMSNorms folded into the QKV / gate-up projections (knob
         # prefill_norm_fold): copies of those weights with the norm weight multiplied into their K
         # columns ((H + 2 kv) D + 2 F) H bf16 per layer, made before the KV cache is sized
@@ -131,8 +136,9 @@ class InferenceEngine:
         # MoE decode on the routed-expert kernels (ops.moe_route / moe_decode_up_swiglu /
         # moe_decode_down_add_rmsnorm): per layer, the pointer tables of the expert weights
         self._moe: Optional[List[Tuple[ops.MoEExpertTable, ops.MoEExpertTable]]] = self._moe_tables()
-        if self._moe is not None and self._w8 is not None:
-            log.info("engine: fp8 decode weights cover the attention projections; the experts stay bf16")
+        if self._moe is not None and self._wq is not None:
+            log.info("engine: %s decode weights cover the attention projections; the experts stay bf16",
+                     self.weight_dtype)
         # the eager MoE module sizes the expert segments on the host: graphs only on the routed kernels
         self.use_graphs = use_graphs and self.device.type == "cuda" and (not cfg.is_moe or self._fused_decode())
         self._graphs: Dict[int, Tuple[torch.cuda.CUDAGraph, Dict[str, torch.Tensor]]] = {}
@@ -490,37 +496,58 @@ class InferenceEngine:
 
     _W8_NAMES = ("wqkv", "wo", "w_up", "w_down")
 
+    @property
+    def _w8(self):
+        """The per-layer fp8 copies (``weight_dtype="fp8"``), else None."""
+        return self._wq if self._wq_kind == "fp8" else None
+
+    @property
+    def _w4(self):
+        """The per-layer int4 copies (``weight_dtype="int4"``), else None."""
+        return self._wq if self._wq_kind == "int4" else None
+
     @torch.no_grad()
-    def _quantize_decode_weights(self) -> List[Dict[str, Tuple[torch.Tensor, torch.Tensor]]]:
-        """Per layer: fp8 (e4m3fn) copies of the decode projection weights + fp32 row scales
-        (``llmctl.plugins.quantizers.quantize_fp8``: absmax / 448 per output row)."""
-        from llmctl.plugins.quantizers import quantize_fp8
+    def _quantize_decode_weights(self, kind: str) -> List[Dict[str, Tuple[torch.Tensor, torch.Tensor]]]:
+        """Per layer: quantised copies of the decode projection weights + their fp32 scales.  ``fp8``:
+        e4m3fn + row scales (``quantizers.quantize_fp8``: absmax / 448 per output row); ``int4``:
+        packed uint8 [N, K/2] + group scales [N, K/128] (``quantizers.quantize_int4_g128``).  A TP
+        rank quantises its own shard; int4 groups run along K and the row-parallel shards cut K at
+        multiples of 128, so the int4 values are the TP=1 engine's."""
+        from llmctl.plugins.quantizers import quantize_fp8, quantize_int4_g128
+
+        quant = quantize_fp8 if kind == "fp8" else quantize_int4_g128
+
+        def copy(w):
+            qd = quant(w.detach())
+            return qd["qweight"].contiguous(), qd["scale"].float().contiguous()
 
         out = []
         for layer in self.model.layers:
             d = {}
             for name in self._W8_NAMES:
                 w = getattr(layer, name, None)
-                # only weights the fused fp8 kernels take (ops.decode_fused_ok: out % 64, in % 128)
+                # only weights the fused kernels take (ops.decode_fused_ok: out % 64, in % 128)
                 if w is None or w.dim() != 2 or w.shape[0] % 64 or w.shape[1] % 128:
                     continue
-                qd = quantize_fp8(w.detach())
-                d[name] = (qd["qweight"].contiguous(), qd["scale"].float().contiguous())
+                d[name] = copy(w)
             out.append(d)
         hw = self.model.head_weight()
         if hw.dim() == 2 and hw.shape[0] % 64 == 0 and hw.shape[1] % 128 == 0:  # the (local shard of the) LM head
-            qd = quantize_fp8(hw.detach())
-            self._w8_head = (qd["qweight"].contiguous(), qd["scale"].float().contiguous())
+            self._wq_head = copy(hw)
+        pairs = [p for d in out for p in d.values()] + ([self._wq_head] if self._wq_head is not None else [])
+        nbytes = sum(t.numel() * t.element_size() for p in pairs for t in p)
+        log.info("engine: %s decode weight copies of %d projections: %.3f GB (out of the KV cache budget)", kind,
+                 len(pairs), nbytes / 1e9)
         return out
 
-    W8_MAX_ROWS = 16  # the fused fp8 decode kernels take at most 16 token rows (ops.decode_fused_ok)
+    W8_MAX_ROWS = 16  # the fused fp8 / int4 decode kernels take at most 16 token rows (ops.decode_fused_ok)
 
     def _dw(self, li: int, layer, name: str, n: int):
-        """(weight, row scales or None) the fused decode path streams for ``layer.name`` at ``n``
-        token rows: the fp8 copy only where the fused fp8 kernel takes it, else the bf16 weight
-        (which is kept) -- never a per-step dequantised fp32 image of the fp8 one."""
-        if self._w8 is not None and 1 <= n <= self.W8_MAX_ROWS and name in self._w8[li]:
-            q = self._w8[li][name]
+        """(weight, scales or None) the fused decode path streams for ``layer.name`` at ``n`` token
+        rows: the fp8 / int4 copy only where the fused kernel takes it, else the bf16 weight (which
+        is kept) -- never a per-step dequantised fp32 image of the copy."""
+        if self._wq is not None and 1 <= n <= self.W8_MAX_ROWS and name in self._wq[li]:
+            q = self._wq[li][name]
             if name not in ("wo", "w_down") or q[0].shape[0] <= 16384:  # add+RMSNorm finalize limit
                 return q
         return getattr(layer, name), None
@@ -533,8 +560,10 @@ class InferenceEngine:
         x = self._embed(ids, positions)
         xn, res = ops.rmsnorm(x, layers[0].attn_norm_w, eps), x
         tp = self.tp > 1
-        def lin(x, w, s):  # a plain decode projection (TP row-parallel partial): bf16 or fp8 weights
-            return ops.decode_linear(x, w) if s is None else ops.decode_linear_fp8(x, w, s)
+        def lin(x, w, s):  # a plain decode projection (TP row-parallel partial): bf16, fp8 or int4 weights
+            if s is None:
+                return ops.decode_linear(x, w)
+            return ops.decode_linear_int4(x, w, s) if w.dtype == torch.uint8 else ops.decode_linear_fp8(x, w, s)
 
         n = ids.shape[0]
         for li, layer in enumerate(layers):
@@ -561,8 +590,8 @@ class InferenceEngine:
                 xn, res = self._reduce_add_rmsnorm(lin(act, wd, sd), layer.b_down, res, nw, eps)
             else:
                 xn, res = ops.decode_linear_add_rmsnorm(act, wd, layer.b_down, res, nw, eps, w_scale=sd)
-        if self._w8_head is not None and n <= self.W8_MAX_ROWS:
-            return self._gather_vocab(ops.decode_linear_fp8(xn, *self._w8_head))
+        if self._wq_head is not None and n <= self.W8_MAX_ROWS:
+            return self._gather_vocab(lin(xn, *self._wq_head))
         return self._gather_vocab(ops.decode_linear(xn, m.head_weight()))
 
     def _bucket(self, n: int) -> int:
@@ -650,7 +679,7 @@ class InferenceEngine:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         self.kv_cache = None
-        self._w8 = self._w8_head = None
+        self._wq = self._wq_head = None
         self._nf = None
         self._moe = None
         self.rope = None

@@ -267,7 +267,7 @@ def main(argv=None) -> int:
     ap.add_argument("--scheduler", default="dynamic")
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--kv-cache-dtype", default="auto")
-    ap.add_argument("--weight-dtype", default="auto")
+    ap.add_argument("--weight-dtype", default="auto", help="auto | fp8 | int4 (decode projection weights)")
     ap.add_argument("--control-timeout", type=float, default=600.0,
                     help="seconds a frozen TP peer may stop heart-beating before the others exit")
     a = ap.parse_args(argv)

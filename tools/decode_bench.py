@@ -60,7 +60,10 @@ def main():
             print(json.dumps(row), flush=True)
         del kc, vc
     os.environ.pop("LLMCTL_DECODE_SPLITS", None)
-    # decode-shaped projection GEMMs (GPT-7B): weight-streaming MFMA kernel vs hipBLASLt
+    # decode-shaped projection GEMMs (GPT-7B): weight-streaming MFMA kernel vs hipBLASLt, and at
+    # M <= 16 the fp8 / int4 weight streams of the fused decode path
+    from llmctl.plugins.quantizers import quantize_fp8, quantize_int4_g128
+
     shapes = {"qkv": (12288, 4096), "o": (4096, 4096), "up": (22016, 4096), "down": (4096, 11008),
               "lm_head": (32000, 4096)}
     for M in (1, 8, 16, 32):
@@ -71,8 +74,21 @@ def main():
             ws = [torch.randn(N, K, device="cuda", dtype=torch.bfloat16) for _ in range(nw)]
             it = iter(range(1 << 30))
             row = {"gemm": name, "M": M, "N": N, "K": K}
-            for impl, fn in (("skinny", lambda: nat.skinny_linear(x, ws[next(it) % nw], None)),
-                             ("hipblaslt", lambda: torch.nn.functional.linear(x, ws[next(it) % nw]))):
+            impls = [("skinny", lambda: nat.skinny_linear(x, ws[next(it) % nw], None), N * K * 2),
+                     ("hipblaslt", lambda: torch.nn.functional.linear(x, ws[next(it) % nw]), N * K * 2)]
+            if M <= 16 and N % 64 == 0:
+                # the fused decode path's quantised weight streams (fp8: e4m3fn + row scales, int4:
+                # group-128 int4 + group scales), again > 768 MB of copies; tbps counts the bytes read
+                for fmt, qf, op in (("fp8", quantize_fp8, nat.decode_linear_fp8),
+                                    ("int4", quantize_int4_g128, nat.decode_linear_int4)):
+                    nq, qs = 2, []
+                    while len(qs) < nq:
+                        d = qf(torch.randn(N, K, device="cuda", dtype=torch.bfloat16))
+                        qs.append((d["qweight"].contiguous(), d["scale"].float().contiguous()))
+                        nbytes = sum(t.numel() * t.element_size() for t in qs[0])
+                        nq = max(2, -(-768 * 2**20 // nbytes))
+                    impls.append((fmt, lambda op=op, qs=qs: op(x, *qs[next(it) % len(qs)], None), nbytes))
+            for impl, fn, nbytes in impls:
                 for _ in range(5):
                     fn()
                 torch.cuda.synchronize()
@@ -84,7 +100,8 @@ def main():
                 torch.cuda.synchronize()
                 us = e0.elapsed_time(e1) / 50 * 1e3
                 row[f"{impl}_us"] = round(us, 1)
-                row[f"{impl}_tbps"] = round(N * K * 2 / (us * 1e-6) / 1e12, 2)
+                row[f"{impl}_tbps"] = round(nbytes / (us * 1e-6) / 1e12, 2)
+            del impls
             rows.append(row)
             print(json.dumps(row), flush=True)
             del ws

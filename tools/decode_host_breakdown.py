@@ -24,7 +24,9 @@ def main():
     ap.add_argument("--prompt", type=int, default=2048)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--kv-cache-dtype", default="auto")
-    ap.add_argument("--weight-dtype", default="auto", help="decode projection weights: auto (bf16) | fp8")
+    ap.add_argument("--weight-dtype", default="auto", help="decode projection weights: auto (bf16) | fp8 | int4")
+    ap.add_argument("--replays", type=int, default=20, help="graph replays per timed window")
+    ap.add_argument("--reps", type=int, default=1, help="timed windows (one JSON line each)")
     a = ap.parse_args()
     import torch
     from llmctl.serve.engine import InferenceEngine
@@ -53,17 +55,18 @@ def main():
                                   "continued": eng.stats.get("async_continued", 0)}), flush=True)
     # device time of one decode step (graph replay incl. in-graph sampling) for this batch
     g, b = eng._graphs[eng._bucket(a.batch)]
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     for _ in range(3):
         g.replay()
-    ev[0].record()
-    for _ in range(20):
-        g.replay()
-    ev[1].record()
-    torch.cuda.synchronize()
-    print(json.dumps({"gpu_ms_per_step": round(ev[0].elapsed_time(ev[1]) / 20, 3), "batch": a.batch,
-                      "context": a.prompt, "kv_cache_dtype": a.kv_cache_dtype,
-                      "weight_dtype": a.weight_dtype}), flush=True)
+    for rep in range(a.reps):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        for _ in range(a.replays):
+            g.replay()
+        ev[1].record()
+        torch.cuda.synchronize()
+        print(json.dumps({"gpu_ms_per_step": round(ev[0].elapsed_time(ev[1]) / a.replays, 3), "batch": a.batch,
+                          "context": a.prompt, "kv_cache_dtype": a.kv_cache_dtype,
+                          "weight_dtype": eng.weight_dtype}), flush=True)
 
 
 if __name__ == "__main__":
