@@ -19,7 +19,11 @@ def run_serving_benchmark(model: str = "gpt-7b", prompt_length: int = 2048, gen_
                           qps: Optional[float] = None, num_requests: int = 16, max_batch_size: int = 16,
                           device: str = "auto", max_batch_tokens: Optional[int] = None, use_graphs: bool = True,
                           seed: int = 0, warmup: bool = True, scheduler: str = "dynamic",
-                          kv_cache_dtype: str = "auto", weight_dtype: str = "auto") -> Dict[str, Any]:
+                          kv_cache_dtype: str = "auto", weight_dtype: str = "auto",
+                          sampling: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+    """``sampling``: extra ``SamplingParams`` fields of every request (penalties, logprobs), to
+    time the extended sampler end to end; the warm-up uses them too, so its graphs are captured
+    before the timed run."""
     import torch
 
     from llmctl.serve.engine import InferenceEngine
@@ -34,13 +38,14 @@ def run_serving_benchmark(model: str = "gpt-7b", prompt_length: int = 2048, gen_
                           weight_dtype=weight_dtype)
     V = eng.cfg.vocab_size
     rng = random.Random(seed)
-    params = SamplingParams(max_tokens=gen_length, temperature=0.0, ignore_eos=True)
+    extra = {k: v for k, v in (sampling or {}).items() if v is not None}
+    params = SamplingParams(max_tokens=gen_length, temperature=0.0, ignore_eos=True, **extra)
     if warmup:  # capture decode graphs, warm the allocator and the GEMM / attention paths of the
         # full-length prefill batches the timed run will form (first-use costs stay out of TTFT)
         eng.generate([[1] * 16 for _ in range(min(max_batch_size, num_requests))],
-                     SamplingParams(max_tokens=4, temperature=0.0, ignore_eos=True))
+                     SamplingParams(max_tokens=4, temperature=0.0, ignore_eos=True, **extra))
         eng.generate([[2] * prompt_length for _ in range(min(max_batch_size, num_requests))],
-                     SamplingParams(max_tokens=2, temperature=0.0, ignore_eos=True))
+                     SamplingParams(max_tokens=2, temperature=0.0, ignore_eos=True, **extra))
     prompts = [[rng.randrange(V) for _ in range(prompt_length)] for _ in range(num_requests)]
     arrivals = [0.0] * num_requests
     if qps:
@@ -82,6 +87,8 @@ def run_serving_benchmark(model: str = "gpt-7b", prompt_length: int = 2048, gen_
         "wall_s": round(wall, 3), "graph_replays": eng.stats["graph_replays"],
         "kv_blocks": eng.kv.num_blocks, "data": "synthetic prompts, random-init weights",
     }
+    if extra:
+        res["sampling"] = extra
     eng.close()
     return res
 

@@ -52,6 +52,10 @@ def e2e(
                                                                  "for prefill_first, 8192 otherwise)"),
     kv_cache_dtype: str = typer.Option("auto", help="KV cache element: auto (model dtype) | fp8 (e4m3fn)"),
     weight_dtype: str = typer.Option("auto", help="Decode projection weights: auto (model dtype) | fp8 (e4m3fn, row scales) | int4 (group-128 scales)"),
+    presence_penalty: float = typer.Option(0.0, help="Presence penalty of every request (extended sampler)"),
+    frequency_penalty: float = typer.Option(0.0, help="Frequency penalty of every request (extended sampler)"),
+    repetition_penalty: float = typer.Option(1.0, help="Repetition penalty of every request (extended sampler)"),
+    logprobs: Optional[int] = typer.Option(None, help="Top logprobs per token, 0..8 (extended sampler)"),
 ) -> None:
     """End-to-end serving benchmark (TTFT p50/p99, TPOT, tokens/s).
 
@@ -64,7 +68,9 @@ def e2e(
     res = run_serving_benchmark(model=model, prompt_length=prompt_length, gen_length=gen_length, qps=qps,
                                 num_requests=num_requests, max_batch_size=max_batch_size, device=device,
                                 scheduler=scheduler, max_batch_tokens=max_batch_tokens, kv_cache_dtype=kv_cache_dtype,
-                                weight_dtype=weight_dtype)
+                                weight_dtype=weight_dtype,
+                                sampling={"presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty,
+                                          "repetition_penalty": repetition_penalty, "logprobs": logprobs})
     console.print_json(json.dumps(res))
 
 

@@ -193,6 +193,179 @@ __global__ __launch_bounds__(256) void sample_kernel(const T* __restrict__ logit
   }
 }
 
+// ---- sample_ext: repetition / frequency / presence penalties, logprobs, device-resident state.
+//
+// Three launches, one 256-thread workgroup per row each: (1) the penalized fp32 row into a
+// scratch buffer, (2) sample_kernel<float> on that scratch (so the draw is bit-for-bit what
+// ``sample`` gives on the penalized row), (3) log-sum-exp, the chosen token's logprob, the nlp
+// largest entries and the count increment.  Per row: state slot s (-1: no state), counts
+// int32 [S, V] = occurrences among generated tokens, prompt_mask uint8 [S, V].
+
+constexpr int kTopLp = 8;  // width of the top-logprob outputs
+
+// 4-wide row accesses (a 32k-vocab row is 32 vector steps per thread instead of 125 scalar ones);
+// taken when V % 4 == 0 and the row pointers are aligned, else the scalar loop covers the row
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+using i32x4 = __attribute__((ext_vector_type(4))) int;
+using u8x4 = __attribute__((ext_vector_type(4))) unsigned char;
+using bf16x4 = __attribute__((ext_vector_type(4))) unsigned short;
+
+__device__ __forceinline__ f32x4 ld4(const unsigned short* p, int c) {
+  const bf16x4 v = reinterpret_cast<const bf16x4*>(p)[c];
+  return f32x4{bf2f(v[0]), bf2f(v[1]), bf2f(v[2]), bf2f(v[3])};
+}
+__device__ __forceinline__ f32x4 ld4(const float* p, int c) { return reinterpret_cast<const f32x4*>(p)[c]; }
+
+template <typename P>
+__device__ __forceinline__ bool aligned(const P* p, int bytes) {
+  return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0;
+}
+
+// fixed order, every step rounded on its own (no FMA contraction): repetition over prompt and
+// output, then frequency, then presence over the output only
+__device__ __forceinline__ float penalized(float x, int c, unsigned char m, float r, float f, float p) {
+  if (m || c > 0) x = x > 0.f ? x / r : __fmul_rn(x, r);
+  x = __fsub_rn(x, __fmul_rn(f, (float)c));
+  return __fsub_rn(x, c > 0 ? p : 0.f);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void penalize_kernel(const T* __restrict__ logits, const int* __restrict__ slot,
+                                                        const float* __restrict__ rep, const float* __restrict__ freq,
+                                                        const float* __restrict__ pres, const int* __restrict__ counts,
+                                                        const unsigned char* __restrict__ pmask,
+                                                        float* __restrict__ out, int V, int S) {
+  const long row = blockIdx.x;
+  const T* lr = logits + row * (long)V;
+  float* xr = out + row * (long)V;
+  const int s = slot[row];
+  const bool vec = (V & 3) == 0 && aligned(lr, 4 * (int)sizeof(T)) && aligned(xr, 16);
+  if (s < 0 || s >= S) {  // stateless row: the fp32 image of the logits
+    const int V4 = vec ? V >> 2 : 0;
+#pragma unroll 4
+    for (int c = threadIdx.x; c < V4; c += 256) reinterpret_cast<f32x4*>(xr)[c] = ld4(lr, c);
+    for (int i = V4 * 4 + threadIdx.x; i < V; i += 256) xr[i] = ld(lr, i);
+    return;
+  }
+  const int* cr = counts + s * (long)V;
+  const unsigned char* mr = pmask + s * (long)V;
+  const float r = rep[row], f = freq[row], p = pres[row];
+  const int V4 = vec && aligned(cr, 16) && aligned(mr, 4) ? V >> 2 : 0;
+#pragma unroll 4
+  for (int c = threadIdx.x; c < V4; c += 256) {
+    f32x4 x = ld4(lr, c);
+    const i32x4 cn = reinterpret_cast<const i32x4*>(cr)[c];
+    const u8x4 m = reinterpret_cast<const u8x4*>(mr)[c];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = penalized(x[e], cn[e], m[e], r, f, p);
+    reinterpret_cast<f32x4*>(xr)[c] = x;
+  }
+  for (int i = V4 * 4 + threadIdx.x; i < V; i += 256) xr[i] = penalized(ld(lr, i), cr[i], mr[i], r, f, p);
+}
+
+// (value, index) arg-max over the workgroup in the order "larger value first, lower index on
+// ties"; an index of INT_MAX means no candidate.  All threads get the result.
+__device__ __forceinline__ void bargmax(float& v, int& idx, float* smv, int* smi) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(v, o);
+    const int oi = __shfl_xor(idx, o);
+    if (oi != 0x7fffffff && (idx == 0x7fffffff || ov > v || (ov == v && oi < idx))) {
+      v = ov;
+      idx = oi;
+    }
+  }
+  if ((threadIdx.x & 63) == 0) {
+    smv[threadIdx.x >> 6] = v;
+    smi[threadIdx.x >> 6] = idx;
+  }
+  __syncthreads();
+  v = smv[0];
+  idx = smi[0];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) {
+    const float ov = smv[w];
+    const int oi = smi[w];
+    if (oi != 0x7fffffff && (idx == 0x7fffffff || ov > v || (ov == v && oi < idx))) {
+      v = ov;
+      idx = oi;
+    }
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void logprob_topk_kernel(const float* __restrict__ x, const int64_t* __restrict__ toks,
+                                                            const int* __restrict__ slot, const int* __restrict__ nlp,
+                                                            int* __restrict__ counts, float* __restrict__ logprob,
+                                                            int* __restrict__ top_ids, float* __restrict__ top_lp,
+                                                            int V, int S) {
+  __shared__ float sm[8];
+  __shared__ float smv[4];
+  __shared__ int smi[4];
+  const long row = blockIdx.x;
+  const float* xr = x + row * (long)V;
+  const int tid = threadIdx.x;
+  const int V4 = (V & 3) == 0 && aligned(xr, 16) ? V >> 2 : 0;  // vector steps; the scalar loops take the rest
+  const f32x4* x4 = reinterpret_cast<const f32x4*>(xr);
+  float mx = -INFINITY;
+#pragma unroll 4
+  for (int c = tid; c < V4; c += 256) {
+    const f32x4 v = x4[c];
+    mx = fmaxf(fmaxf(mx, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
+  }
+  for (int i = V4 * 4 + tid; i < V; i += 256) mx = fmaxf(mx, xr[i]);
+  mx = bmax(mx, sm);
+  float z = 0.f;
+#pragma unroll 4
+  for (int c = tid; c < V4; c += 256) {
+    const f32x4 v = x4[c];
+    z += (__expf(v[0] - mx) + __expf(v[1] - mx)) + (__expf(v[2] - mx) + __expf(v[3] - mx));
+  }
+  for (int i = V4 * 4 + tid; i < V; i += 256) z += __expf(xr[i] - mx);
+  z = block_sum<4>(z, sm);
+  const float lz = logf(z);  // logsumexp = mx + lz; x - logsumexp is taken as (x - mx) - lz
+  const int tok = (int)toks[row];
+  if (tid == 0) logprob[row] = (xr[tok] - mx) - lz;
+  // the nlp largest entries by repeated arg-max: round j takes the best entry that comes after
+  // round j - 1's pick in (value descending, index ascending) order
+  const int n = min(max(nlp[row], 0), kTopLp);
+  float pv = INFINITY;
+  int pi = -1;
+  for (int j = 0; j < kTopLp; ++j) {
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    if (j < n && pi != 0x7fffffff) {  // uniform over the workgroup
+      // index order within the thread: strict > keeps the lowest index
+      auto take = [&](float v, int i) {
+        if ((v < pv || (v == pv && i > pi)) && (bi == 0x7fffffff || v > bv)) {
+          bv = v;
+          bi = i;
+        }
+      };
+#pragma unroll 4
+      for (int c = tid; c < V4; c += 256) {
+        const f32x4 v = x4[c];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) take(v[e], c * 4 + e);
+      }
+      for (int i = V4 * 4 + tid; i < V; i += 256) take(xr[i], i);
+      bargmax(bv, bi, smv, smi);
+    }
+    if (tid == 0) {
+      const bool ok = bi != 0x7fffffff;
+      top_ids[row * kTopLp + j] = ok ? bi : -1;
+      top_lp[row * kTopLp + j] = ok ? (bv - mx) - lz : -INFINITY;
+    }
+    pv = bv;
+    pi = bi;
+  }
+  const int s = slot[row];
+  if (tid == 0 && s >= 0 && s < S) {  // after everything above; rows of a launch never share a slot
+    int* c = counts + s * (long)V + tok;
+    *c = *c + 1;
+  }
+}
+
 }  // namespace
 
 at::Tensor sample(const at::Tensor& logits, const at::Tensor& temperature, const at::Tensor& top_k,
@@ -220,6 +393,60 @@ at::Tensor sample(const at::Tensor& logits, const at::Tensor& temperature, const
   return out;
 }
 
-TORCH_LIBRARY_IMPL(llmctl, CUDA, m) { m.impl("sample", &sample); }
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> sample_ext(
+    const at::Tensor& logits, const at::Tensor& temperature, const at::Tensor& top_k, const at::Tensor& top_p,
+    const at::Tensor& uniform, const at::Tensor& slot, const at::Tensor& rep, const at::Tensor& freq,
+    const at::Tensor& pres, const at::Tensor& nlp, at::Tensor& counts, const at::Tensor& prompt_mask) {
+  LLMCTL_CHECK(logits.dim() == 2 && logits.is_contiguous(), "logits: contiguous [N, V]");
+  const int N = logits.size(0), V = logits.size(1);
+  LLMCTL_CHECK(V >= 1, "logits: V >= 1");
+  LLMCTL_CHECK(temperature.scalar_type() == at::kFloat && top_p.scalar_type() == at::kFloat &&
+                   uniform.scalar_type() == at::kFloat && top_k.scalar_type() == at::kInt,
+               "temperature/top_p/uniform fp32, top_k int32");
+  LLMCTL_CHECK(rep.scalar_type() == at::kFloat && freq.scalar_type() == at::kFloat &&
+                   pres.scalar_type() == at::kFloat && slot.scalar_type() == at::kInt && nlp.scalar_type() == at::kInt,
+               "rep/freq/pres fp32, slot/nlp int32");
+  for (const at::Tensor* t : {&temperature, &top_k, &top_p, &uniform, &slot, &rep, &freq, &pres, &nlp})
+    LLMCTL_CHECK(t->numel() == N && t->is_contiguous() && t->device() == logits.device(),
+                 "per-row parameter tensors must have N elements on the logits' device");
+  LLMCTL_CHECK(counts.dim() == 2 && counts.size(1) == V && counts.scalar_type() == at::kInt && counts.is_contiguous() &&
+                   counts.device() == logits.device(),
+               "counts: contiguous int32 [S, V] on the logits' device");
+  LLMCTL_CHECK(prompt_mask.dim() == 2 && prompt_mask.size(0) == counts.size(0) && prompt_mask.size(1) == V &&
+                   prompt_mask.scalar_type() == at::kByte && prompt_mask.is_contiguous() &&
+                   prompt_mask.device() == logits.device(),
+               "prompt_mask: contiguous uint8 [S, V] on the logits' device");
+  const int S = counts.size(0);
+  const c10::DeviceGuard g(logits.device());
+  auto toks = at::empty({N}, logits.options().dtype(at::kLong));
+  auto logprob = at::empty({N}, logits.options().dtype(at::kFloat));
+  auto top_ids = at::empty({N, kTopLp}, logits.options().dtype(at::kInt));
+  auto top_lp = at::empty({N, kTopLp}, logits.options().dtype(at::kFloat));
+  if (N == 0) return {toks, logprob, top_ids, top_lp};
+  auto x = at::empty({N, V}, logits.options().dtype(at::kFloat));  // the penalized rows
+  const hipStream_t st = stream();
+  if (logits.scalar_type() == at::kBFloat16)
+    hipLaunchKernelGGL(penalize_kernel<unsigned short>, dim3(N), dim3(256), 0, st, bf_ptr(logits),
+                       slot.data_ptr<int>(), rep.data_ptr<float>(), freq.data_ptr<float>(), pres.data_ptr<float>(),
+                       counts.data_ptr<int>(), prompt_mask.data_ptr<unsigned char>(), x.data_ptr<float>(), V, S);
+  else if (logits.scalar_type() == at::kFloat)
+    hipLaunchKernelGGL(penalize_kernel<float>, dim3(N), dim3(256), 0, st, logits.data_ptr<float>(),
+                       slot.data_ptr<int>(), rep.data_ptr<float>(), freq.data_ptr<float>(), pres.data_ptr<float>(),
+                       counts.data_ptr<int>(), prompt_mask.data_ptr<unsigned char>(), x.data_ptr<float>(), V, S);
+  else
+    LLMCTL_CHECK(false, "logits must be bf16 or fp32");
+  hipLaunchKernelGGL(sample_kernel<float>, dim3(N), dim3(256), 0, st, x.data_ptr<float>(),
+                     temperature.data_ptr<float>(), top_k.data_ptr<int>(), top_p.data_ptr<float>(),
+                     uniform.data_ptr<float>(), toks.data_ptr<int64_t>(), V);
+  hipLaunchKernelGGL(logprob_topk_kernel, dim3(N), dim3(256), 0, st, x.data_ptr<float>(), toks.data_ptr<int64_t>(),
+                     slot.data_ptr<int>(), nlp.data_ptr<int>(), counts.data_ptr<int>(), logprob.data_ptr<float>(),
+                     top_ids.data_ptr<int>(), top_lp.data_ptr<float>(), V, S);
+  return {toks, logprob, top_ids, top_lp};
+}
+
+TORCH_LIBRARY_IMPL(llmctl, CUDA, m) {
+  m.impl("sample", &sample);
+  m.impl("sample_ext", &sample_ext);
+}
 
 }  // namespace llmctl

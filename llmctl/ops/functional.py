@@ -683,12 +683,38 @@ def sample(logits, temperature, top_k, top_p, uniform):
     return ref.sample(logits, temperature, top_k, top_p, uniform)
 
 
+def sample_ext(logits, temperature, top_k, top_p, uniform, slot, rep, freq, pres, nlp, counts, prompt_mask,
+               check_slots: bool = True):
+    """``sample`` with repetition / frequency / presence penalties, logprobs and device-resident
+    per-sequence state (semantics: ``ref.sample_ext``): ``(tokens int64 [N], logprob f32 [N],
+    top_ids int32 [N, 8], top_lp f32 [N, 8])``; ``counts`` is updated in place.  Like ``sample``
+    it neither syncs with the host nor keeps state of its own, so it can be captured in a graph.
+    Outside a capture ``check_slots`` verifies (one host sync) that the rows' slots are in range
+    and distinct; a caller that owns the slot allocation may skip it."""
+    if use_native(logits):
+        if check_slots and not torch.cuda.is_current_stream_capturing():
+            s = slot[slot >= 0]
+            if s.numel() and (int(s.max()) >= counts.shape[0] or torch.unique(s).numel() != s.numel()):
+                raise ValueError(f"sample_ext: state slots must be distinct and below {counts.shape[0]}, "
+                                 f"got {slot.tolist()}")
+        toks, logprob, top_ids, top_lp = native().sample_ext(logits, temperature, top_k, top_p, uniform, slot, rep,
+                                                              freq, pres, nlp, counts, prompt_mask)
+        return toks, logprob, top_ids, top_lp
+    return ref.sample_ext(logits, temperature, top_k, top_p, uniform, slot, rep, freq, pres, nlp, counts, prompt_mask)
+
+
+def sampler_state_reset(counts, prompt_mask, slot: int, prompt_ids, output_ids) -> None:
+    """Initialise slot ``slot`` of the ``sample_ext`` state from a sequence's prompt and generated
+    tokens (once per admission or resumption: plain torch, enqueued on the current stream)."""
+    ref.sampler_state_reset(counts, prompt_mask, slot, prompt_ids, output_ids)
+
+
 __all__ = [
     "transpose_",
     "rmsnorm", "add_rmsnorm", "layernorm", "add_layernorm", "rope_qkv", "flash_attention", "rope_flash_attention",
     "swiglu",
     "gelu", "cross_entropy", "adamw_step_", "l2norm_sq", "kv_cache_write", "paged_attention_decode",
-    "sample", "decode_linear", "decode_linear_fp8", "decode_linear_int4", "decode_fused_ok", "decode_qkv_rope_cache", "decode_up_swiglu", "decode_attention_qkv", "up_swiglu",
+    "sample", "sample_ext", "sampler_state_reset", "decode_linear", "decode_linear_fp8", "decode_linear_int4", "decode_fused_ok", "decode_qkv_rope_cache", "decode_up_swiglu", "decode_attention_qkv", "up_swiglu",
     "decode_linear_add_rmsnorm", "rope_qkv_cache", "paged_prefill_attention", "prefill_work_list", "attn_merge_",
     "rms_rstd", "rowscale_ok", "linear_rowscale", "up_swiglu_rowscale", "linear_acc_",
     "MoEExpertTable", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",

@@ -377,6 +377,86 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
     return out
 
 
+TOP_LOGPROBS = 8  # width of the top-logprob outputs of ``sample_ext``
+
+
+def penalize(logits: torch.Tensor, slot: torch.Tensor, rep: torch.Tensor, freq: torch.Tensor, pres: torch.Tensor,
+             counts: torch.Tensor, prompt_mask: torch.Tensor) -> torch.Tensor:
+    """Step 1 of :func:`sample_ext`: the penalized fp32 rows ``x [N, V]`` (``counts`` is only read)."""
+    x = logits.float().clone()
+    for i in range(x.shape[0]):
+        s = int(slot[i])
+        if s < 0:
+            continue
+        c = counts[s]
+        xi = x[i]
+        seen = (prompt_mask[s] != 0) | (c > 0)
+        xi = torch.where(seen, torch.where(xi > 0, xi / rep[i], xi * rep[i]), xi)
+        xi = xi - freq[i] * c.float()
+        xi = xi - pres[i] * (c > 0).float()
+        x[i] = xi
+    return x
+
+
+def sample_ext(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
+               uniform: torch.Tensor, slot: torch.Tensor, rep: torch.Tensor, freq: torch.Tensor, pres: torch.Tensor,
+               nlp: torch.Tensor, counts: torch.Tensor, prompt_mask: torch.Tensor):
+    """:func:`sample` with repetition / frequency / presence penalties, logprobs and per-sequence
+    state; returns ``(tokens int64 [N], logprob f32 [N], top_ids int32 [N, 8], top_lp f32 [N, 8])``
+    and MUTATES ``counts``.
+
+    Per row: logits ``l [V]`` (bf16 or fp32), a state slot ``s`` (``-1``: no state, no penalties,
+    no update), ``rep > 0``, ``freq``, ``pres`` (fp32) and ``nlp`` in 0..8.  The state is ``counts
+    int32 [S, V]`` (occurrences among the generated tokens) and ``prompt_mask uint8 [S, V]`` (the
+    token occurs in the prompt).  Semantics (shared with ``csrc/sampling.hip``):
+
+    1. ``x = float(l)``; for a row with ``s >= 0``, in fp32 and in exactly this order:
+       a. if ``prompt_mask[s, v] or counts[s, v] > 0``: ``x = x / rep if x > 0 else x * rep``;
+       b. ``x = x - freq * counts[s, v]``;
+       c. ``x = x - pres * (counts[s, v] > 0)``
+       (the HF / vLLM convention: repetition sees prompt and output, frequency and presence the
+       output only);
+    2. the token is drawn from ``x`` by the rule of :func:`sample` (temperature, top-k, top-p, the
+       caller's uniform, greedy at ``T <= 0``, lowest index on ties), with the arithmetic of
+       ``sample`` on an fp32 row holding ``x``;
+    3. ``logprob = x[tok] - logsumexp(x)``: after the penalties, before the temperature (the
+       logsumexp is taken in fp64 here and returned as fp32);
+    4. the ``nlp`` largest ``x`` as ``(id, x - logsumexp)`` in descending order, ties to the lowest
+       index; entries past ``nlp`` hold id ``-1`` and logprob ``-inf``;
+    5. for a row with ``s >= 0``: ``counts[s, tok] += 1``, after everything above.  No two rows of
+       a call may share a slot."""
+    N, V = logits.shape
+    x = penalize(logits, slot, rep, freq, pres, counts, prompt_mask)
+    toks = sample(x, temperature, top_k, top_p, uniform)
+    lp = x.double() - torch.logsumexp(x.double(), dim=1, keepdim=True)
+    logprob = lp.gather(1, toks.view(N, 1)).view(N).float()
+    top_ids = torch.full((N, TOP_LOGPROBS), -1, dtype=torch.int32, device=logits.device)
+    top_lp = torch.full((N, TOP_LOGPROBS), -float("inf"), dtype=torch.float32, device=logits.device)
+    order = torch.sort(x, dim=1, descending=True, stable=True).indices  # stable: lowest index first on ties
+    for i in range(N):
+        k = min(max(int(nlp[i]), 0), TOP_LOGPROBS, V)
+        top_ids[i, :k] = order[i, :k].to(torch.int32)
+        top_lp[i, :k] = lp[i, order[i, :k]].float()
+        s = int(slot[i])
+        if s >= 0:
+            counts[s, int(toks[i])] += 1
+    return toks, logprob, top_ids, top_lp
+
+
+def sampler_state_reset(counts: torch.Tensor, prompt_mask: torch.Tensor, slot: int, prompt_ids, output_ids) -> None:
+    """Slot ``slot`` of the ``sample_ext`` state as it stands after ``prompt_ids`` were given and
+    ``output_ids`` generated: both rows zeroed, then the prompt's tokens marked and the generated
+    ones counted."""
+    counts[slot].zero_()
+    prompt_mask[slot].zero_()
+    d = counts.device
+    if len(prompt_ids):
+        prompt_mask[slot].index_fill_(0, torch.as_tensor(list(prompt_ids), dtype=torch.long).to(d), 1)
+    if len(output_ids):
+        idx = torch.as_tensor(list(output_ids), dtype=torch.long).to(d)
+        counts[slot].index_add_(0, idx, torch.ones(len(output_ids), dtype=counts.dtype, device=d))
+
+
 # ----------------------------------------------------------------------------- int4 decode weights
 def dequant_int4_g128(qweight: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     """fp32 ``[N, K]`` image of a group-128 int4 weight (``quantizers.quantize_int4_g128``):

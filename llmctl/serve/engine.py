@@ -18,7 +18,9 @@ prompts), and sampled with a host sync per request per token.  Here:
   the whole decode step (embedding .. lm_head) is captured once per batch-size bucket in
   a HIP graph and replayed with static input buffers (no per-layer launch overhead);
 * sampling: one batched kernel (temperature / top-k / top-p / greedy) with uniforms drawn
-  once per step; the only host sync per step is reading the sampled ids.
+  once per step; the only host sync per step is reading the sampled ids.  Requests with
+  repetition / presence / frequency penalties or logprobs sample through ``ops.sample_ext``,
+  which keeps the per-sequence token counts on the device and returns the logprobs with the ids.
 """
 
 from __future__ import annotations
@@ -142,6 +144,18 @@ class InferenceEngine:
         # the eager MoE module sizes the expert segments on the host: graphs only on the routed kernels
         self.use_graphs = use_graphs and self.device.type == "cuda" and (not cfg.is_moe or self._fused_decode())
         self._graphs: Dict[int, Tuple[torch.cuda.CUDAGraph, Dict[str, torch.Tensor]]] = {}
+        # batches with an extended row (penalties / logprobs, ``SamplingParams.extended``) replay a
+        # second graph per bucket whose body samples with ``ops.sample_ext``; plain batches never
+        # touch it.  The penalties' per-sequence state (token counts int32 + prompt mask uint8,
+        # [max_batch_size, V]) lives on the device -- an asynchronous step is launched before the
+        # previous step's tokens reach the host -- and is allocated on first need.
+        self._graphs_ext: Dict[int, Tuple[torch.cuda.CUDAGraph, Dict[str, torch.Tensor]]] = {}
+        self._sampler_state: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+        self._sampler_free: List[int] = []
+        self._ext_step: Optional[Dict[str, np.ndarray]] = None  # the extended fields of the step being launched
+        self._ext_out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None  # its logprob outputs
+        self._host_lp: Optional[List] = None  # logprob rows of the last host-sampled batch
+        self.scheduler.on_release = self._release_sampler_slot
         # sampling uniforms come from the host (one H2D copy with the step's other inputs), so
         # in-graph sampling and the eager path draw the same stream
         self._np_rng = np.random.default_rng(seed)
@@ -602,6 +616,25 @@ class InferenceEngine:
 
     _STAGED = ("ids", "positions", "slots", "block_tables", "ctx_lens", "u")
 
+    _EXT = ("slot", "rep", "freq", "pres", "nlp")  # per-row inputs of ops.sample_ext, in argument order
+    _EXT_OUT = ("lp", "top_ids", "top_lp")  # its logprob outputs
+
+    def _static_ext(self, nb: int, bufs: Dict) -> None:
+        """The extended graph's additional static buffers: the per-row ``sample_ext`` parameters
+        (neutral defaults: no state, no penalties, no top list) and two pinned host sets for the
+        logprob outputs, flipped with ``host_toks``."""
+        d = self.device
+        bufs["slot"] = torch.full((nb,), -1, dtype=torch.int32, device=d)
+        bufs["rep"] = torch.ones(nb, dtype=torch.float32, device=d)
+        bufs["freq"] = torch.zeros(nb, dtype=torch.float32, device=d)
+        bufs["pres"] = torch.zeros(nb, dtype=torch.float32, device=d)
+        bufs["nlp"] = torch.zeros(nb, dtype=torch.int32, device=d)
+        W = ops.ref.TOP_LOGPROBS
+        host = lambda: {"lp": torch.zeros(nb, dtype=torch.float32).pin_memory(),
+                        "top_ids": torch.zeros(nb, W, dtype=torch.int32).pin_memory(),
+                        "top_lp": torch.zeros(nb, W, dtype=torch.float32).pin_memory()}
+        bufs["host_lp"] = [host(), host()]
+
     def _static(self, nb: int) -> Dict:
         d = self.device
         bufs = {"ids": torch.zeros(nb, dtype=torch.long, device=d),
@@ -637,11 +670,19 @@ class InferenceEngine:
         asynchronous path launches step N + 1 without reading step N's tokens first)."""
         bufs["logits"] = self._decode_body(bufs["ids"], bufs["positions"], bufs["slots"], bufs["block_tables"],
                                            bufs["ctx_lens"])
-        bufs["toks"] = ops.sample(bufs["logits"].contiguous(), bufs["temp"], bufs["topk"], bufs["topp"], bufs["u"])
+        if "slot" in bufs:  # the extended graph: penalties, logprobs and the state update ride in the sampler
+            counts, mask = self._sampler_state
+            bufs["toks"], bufs["lp"], bufs["top_ids"], bufs["top_lp"] = ops.sample_ext(
+                bufs["logits"].contiguous(), bufs["temp"], bufs["topk"], bufs["topp"], bufs["u"],
+                *(bufs[k] for k in self._EXT), counts, mask, check_slots=False)
+        else:
+            bufs["toks"] = ops.sample(bufs["logits"].contiguous(), bufs["temp"], bufs["topk"], bufs["topp"], bufs["u"])
         bufs["ids"].copy_(bufs["toks"])
 
-    def _capture(self, nb: int):
+    def _capture(self, nb: int, ext: bool = False):
         bufs = self._static(nb)
+        if ext:
+            self._static_ext(nb, bufs)
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
@@ -651,16 +692,17 @@ class InferenceEngine:
         g = torch.cuda.CUDAGraph()
         with graph_capture_gc_guard(), torch.cuda.graph(g):
             self._graph_body(bufs)
-        self._graphs[nb] = (g, bufs)
+        (self._graphs_ext if ext else self._graphs)[nb] = (g, bufs)
 
     def release_graphs(self) -> None:
         """Drop the captured decode graphs (they hold the RCCL communicator's captured
         collectives: release them before ``destroy_process_group``)."""
-        if self._graphs and self.device.type == "cuda":
+        if (self._graphs or self._graphs_ext) and self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
-        for g, _ in self._graphs.values():
-            g.reset()
-        self._graphs.clear()
+        for graphs in (self._graphs, self._graphs_ext):
+            for g, _ in graphs.values():
+                g.reset()
+            graphs.clear()
 
     def close(self) -> None:
         """Deterministic teardown, never left to garbage collection: drop an in-flight pipelined
@@ -675,9 +717,12 @@ class InferenceEngine:
     def _release_resources(self) -> None:
         self._pending = None
         self._last_toks = None
+        self._ext_out = None
         self.release_graphs()
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
+        self._sampler_state = None
+        self._sampler_free = []
         self.kv_cache = None
         self._wq = self._wq_head = None
         self._nf = None
@@ -725,9 +770,13 @@ class InferenceEngine:
         engine configuration consumes: one uniform per sampled row)."""
         n = len(plan["positions"])
         nb = self._bucket(n)
-        if nb not in self._graphs:
-            self._capture(nb)
-        g, b = self._graphs[nb]
+        # a step with extended rows (``_launch_decode`` set ``_ext_step``) replays the bucket's
+        # extended graph; its per-row penalty parameters follow the ``params_key`` rule below
+        ext = self._ext_step if "temp" in plan else None
+        graphs = self._graphs_ext if ext is not None else self._graphs
+        if nb not in graphs:
+            self._capture(nb, ext is not None)
+        g, b = graphs[nb]
         h = b["stage"][b["flip"]]
         b["flip"] ^= 1
         hn = {k: v.numpy() for k, v in h.items()}
@@ -743,6 +792,16 @@ class InferenceEngine:
         if "temp" in plan:
             key = (np.asarray(plan["temp"], dtype=np.float32).tobytes(), np.asarray(plan["topk"], dtype=np.int32).tobytes(),
                    np.asarray(plan["topp"], dtype=np.float32).tobytes())
+            if ext is not None:
+                key += tuple(ext[k].tobytes() for k in self._EXT)
+            if ext is not None and b["params_key"] != key:
+                b["slot"].fill_(-1)
+                b["rep"].fill_(1.0)
+                b["freq"].zero_()
+                b["pres"].zero_()
+                b["nlp"].zero_()
+                for k in self._EXT:
+                    b[k][:n].copy_(torch.from_numpy(ext[k]).to(self.device))
             if b["params_key"] != key:
                 d = self.device
                 b["temp"].zero_()
@@ -789,20 +848,36 @@ class InferenceEngine:
                     **self._sampling_fields(seqs))
         if cont:
             plan.setdefault("ids", np.zeros(n, dtype=np.int64))
-        toks = self._decode_sample_exec(self._publish(plan))
+        # extended rows: their fields stay on this rank (TP > 1 refuses such requests) and reach
+        # the step beside the plan; slots are assigned, and their resets enqueued, here
+        ext = self._ext_fields(seqs)
+        self._ext_step = ext
+        try:
+            toks = self._decode_sample_exec(self._publish(plan))
+        finally:
+            self._ext_step = None
+        want_lp = ext is not None and any(s.params.logprobs is not None for s in seqs)
         d = self.device
+        host_lp = None
         if self._graph_ok(n):
-            b = self._graphs[self._bucket(n)][1]
+            b = (self._graphs_ext if ext is not None else self._graphs)[self._bucket(n)][1]
             out = b["host_toks"][b["tflip"]]
+            if want_lp:  # the logprobs ride the same pinned D2H copy as the tokens
+                host_lp = b["host_lp"][b["tflip"]]
+                for k in self._EXT_OUT:
+                    host_lp[k].copy_(b[k], non_blocking=True)
             b["tflip"] ^= 1
             out.copy_(toks, non_blocking=True)
         else:
             out = toks.to("cpu", non_blocking=True) if d.type == "cuda" else toks
+            if want_lp:
+                host_lp = {k: (t.to("cpu", non_blocking=True) if d.type == "cuda" else t)
+                           for k, t in zip(self._EXT_OUT, self._ext_out)}
         ev = None
         if d.type == "cuda":
             ev = torch.cuda.Event()
             ev.record()
-        return {"seqs": list(seqs), "host": out, "event": ev, "n": n}
+        return {"seqs": list(seqs), "host": out, "host_lp": host_lp, "event": ev, "n": n}
 
     @torch.inference_mode()
     def _decode_sample_exec(self, plan: Dict) -> torch.Tensor:
@@ -825,7 +900,15 @@ class InferenceEngine:
         topk = torch.from_numpy(np.asarray(plan["topk"], dtype=np.int32)).to(d)
         topp = torch.from_numpy(np.asarray(plan["topp"], dtype=np.float32)).to(d)
         u = torch.from_numpy(np.asarray(plan["u"], dtype=np.float32)).to(d)
-        toks = ops.sample(logits[:n].contiguous(), temp, topk, topp, u)
+        ext = self._ext_step
+        if ext is None:
+            toks = ops.sample(logits[:n].contiguous(), temp, topk, topp, u)
+        else:
+            counts, mask = self._sampler_state
+            toks, lp, top_ids, top_lp = ops.sample_ext(logits[:n].contiguous(), temp, topk, topp, u,
+                                                       *(torch.from_numpy(ext[k]).to(d) for k in self._EXT), counts,
+                                                       mask, check_slots=False)
+            self._ext_out = (lp, top_ids, top_lp)
         self._last_toks = toks
         return toks
 
@@ -834,12 +917,15 @@ class InferenceEngine:
         if p["event"] is not None:
             p["event"].synchronize()
         toks = p["host"][: p["n"]].tolist()
+        lps = None
+        if p.get("host_lp") is not None:
+            lps = self._lp_rows(p["seqs"], *(p["host_lp"][k][: p["n"]].tolist() for k in self._EXT_OUT))
         produced = 0
-        for seq, tok in zip(p["seqs"], toks):
+        for i, (seq, tok) in enumerate(zip(p["seqs"], toks)):
             if seq.status != "running":  # finished by the previous step's tokens: speculative row
                 continue
             self.scheduler.computed(seq, 1)
-            self._append(seq, tok)
+            self._append(seq, tok, lps[i] if lps else None)
             produced += 1
         return produced
 
@@ -894,7 +980,76 @@ class InferenceEngine:
             self._sample_params = cached = (key, temp, topk, topp)
         _, temp, topk, topp = cached
         u = torch.from_numpy(self._np_rng.random(n, dtype=np.float32)).to(d)
-        return ops.sample(logits.contiguous(), temp, topk, topp, u)
+        self._host_lp = None
+        ext = self._ext_fields(seqs)
+        if ext is None:
+            return ops.sample(logits.contiguous(), temp, topk, topp, u)
+        counts, mask = self._sampler_state
+        toks, lp, top_ids, top_lp = ops.sample_ext(logits.contiguous(), temp, topk, topp, u,
+                                                   *(torch.from_numpy(ext[k]).to(d) for k in self._EXT), counts, mask,
+                                                   check_slots=False)
+        if any(s.params.logprobs is not None for s in seqs):  # read with the tokens (this path syncs anyway)
+            self._host_lp = self._lp_rows(seqs, lp.tolist(), top_ids.tolist(), top_lp.tolist())
+        return toks
+
+    def _take_host_lp(self) -> Optional[List]:
+        """The logprob rows :meth:`_sample_rows` left for the batch just sampled (None: no row
+        asked for logprobs, or an instance-level ``sample`` override did the sampling)."""
+        lps, self._host_lp = self._host_lp, None
+        return lps
+
+    # ------------------------------------------------------------------ extended sampling
+    def _sampler_vocab(self) -> int:
+        return self.model.head_weight().shape[0] * self.tp
+
+    def _ext_fields(self, seqs: List[Sequence]) -> Optional[Dict[str, np.ndarray]]:
+        """The per-row ``ops.sample_ext`` inputs of a batch, or None when no row is extended (the
+        batch then samples exactly as before).  Plain rows get the neutral values (slot -1).  A
+        penalized sequence without a state slot takes one here and has it initialised from its
+        prompt and the tokens generated so far -- admission and resumption after preemption alike;
+        the reset is enqueued on the engine's stream, behind any speculative row of an in-flight
+        step that still writes to a recycled slot."""
+        if not any(s.params.extended for s in seqs):
+            return None
+        if self._sampler_state is None:
+            S, V = self.max_batch_size, self._sampler_vocab()
+            self._sampler_state = (torch.zeros(S, V, dtype=torch.int32, device=self.device),
+                                   torch.zeros(S, V, dtype=torch.uint8, device=self.device))
+            self._sampler_free = list(range(S - 1, -1, -1))
+            log.info("engine: sampler state for penalties: %d slots x %d tokens, %.2f MB", S, V, S * V * 5 / 1e6)
+        counts, mask = self._sampler_state
+        n = len(seqs)
+        ext = {"slot": np.full(n, -1, dtype=np.int32), "rep": np.ones(n, dtype=np.float32),
+               "freq": np.zeros(n, dtype=np.float32), "pres": np.zeros(n, dtype=np.float32),
+               "nlp": np.zeros(n, dtype=np.int32)}
+        for i, s in enumerate(seqs):
+            p = s.params
+            if p.penalized:
+                if s.sampler_slot < 0:
+                    if not self._sampler_free:
+                        raise RuntimeError(f"no free sampler-state slot ({self.max_batch_size} penalized "
+                                           "sequences are already running)")
+                    s.sampler_slot = self._sampler_free.pop()
+                    ops.sampler_state_reset(counts, mask, s.sampler_slot, s.prompt_ids, s.output_ids)
+                ext["slot"][i] = s.sampler_slot
+                ext["rep"][i], ext["freq"][i], ext["pres"][i] = p.repetition_penalty, p.frequency_penalty, p.presence_penalty
+            if p.logprobs is not None:
+                ext["nlp"][i] = min(max(int(p.logprobs), 0), ops.ref.TOP_LOGPROBS)
+        return ext
+
+    def _release_sampler_slot(self, seq: Sequence) -> None:
+        """Scheduler hook: ``seq`` finished or was preempted; its state slot returns to the free list."""
+        if seq.sampler_slot >= 0:
+            self._sampler_free.append(seq.sampler_slot)
+            seq.sampler_slot = -1
+
+    @staticmethod
+    def _lp_rows(seqs: List[Sequence], lp: List[float], top_ids: List[List[int]], top_lp: List[List[float]]):
+        """Per row: None, or ``(logprob, [(token id, logprob), ...])`` with the sequence's
+        ``logprobs`` most likely tokens."""
+        return [None if s.params.logprobs is None else
+                (lp[i], [(t, v) for t, v in zip(top_ids[i], top_lp[i]) if t >= 0])
+                for i, s in enumerate(seqs)]
 
     # ------------------------------------------------------------------ step loop
     def add_request(self, prompt_ids: List[int], params: SamplingParams, request_id: str = "", on_token=None,
@@ -904,11 +1059,15 @@ class InferenceEngine:
         self.scheduler.add(seq)
         return seq
 
-    def _append(self, seq: Sequence, tok: int) -> None:
+    def _append(self, seq: Sequence, tok: int, lp=None) -> None:
+        """``lp``: the token's row of :meth:`_lp_rows` (a sequence with ``logprobs`` set)."""
         now = time.time()
         if seq.first_token_time is None:
             seq.first_token_time = now
         seq.output_ids.append(tok)
+        if seq.params.logprobs is not None:  # kept in step with output_ids (before on_token reads them)
+            seq.output_logprobs.append(lp[0] if lp is not None else float("nan"))
+            seq.output_top_logprobs.append(lp[1] if lp is not None else [])
         if seq.on_token:
             seq.on_token(seq, tok)
         eos = getattr(self.tokenizer, "eos_token_id", None)
@@ -944,14 +1103,15 @@ class InferenceEngine:
             logits = self.mixed(out.prefill, out.decode)
             final = [c.seq for c in out.prefill if c.final]
             toks = self.sample(logits, final + list(out.decode))
+            lps = self._take_host_lp()
             for c in out.prefill:
                 self.scheduler.computed(c.seq, c.count)
                 self.stats["prefix_hit_tokens"] = self.stats.get("prefix_hit_tokens", 0) + (
                     c.seq.cached_tokens if c.start == c.seq.cached_tokens else 0)
             for seq in out.decode:
                 self.scheduler.computed(seq, 1)
-            for seq, tok in zip(final + list(out.decode), toks):
-                self._append(seq, tok)
+            for i, (seq, tok) in enumerate(zip(final + list(out.decode), toks)):
+                self._append(seq, tok, lps[i] if lps else None)
                 produced += 1
             self.stats["steps"] += 1
             return produced
@@ -967,9 +1127,11 @@ class InferenceEngine:
             return produced + self._finalize(pend)
         if out.decode:
             logits = self.decode(out.decode)
-            for seq, tok in zip(out.decode, self.sample(logits, out.decode)):
+            toks = self.sample(logits, out.decode)
+            lps = self._take_host_lp()
+            for i, (seq, tok) in enumerate(zip(out.decode, toks)):
                 self.scheduler.computed(seq, 1)
-                self._append(seq, tok)
+                self._append(seq, tok, lps[i] if lps else None)
                 produced += 1
         if out.prefill:
             logits = self.prefill(out.prefill)
@@ -979,8 +1141,10 @@ class InferenceEngine:
                 self.stats["prefix_hit_tokens"] = self.stats.get("prefix_hit_tokens", 0) + (
                     c.seq.cached_tokens if c.start == c.seq.cached_tokens else 0)
             if final:
-                for seq, tok in zip(final, self.sample(logits, final)):
-                    self._append(seq, tok)
+                toks = self.sample(logits, final)
+                lps = self._take_host_lp()
+                for i, (seq, tok) in enumerate(zip(final, toks)):
+                    self._append(seq, tok, lps[i] if lps else None)
                     produced += 1
         self.stats["steps"] += 1
         return produced

@@ -43,6 +43,23 @@ class SamplingParams:
     stop: List[str] = field(default_factory=list)
     ignore_eos: bool = False
     seed: Optional[int] = None
+    # the extended sampler (``ops.sample_ext``): repetition over prompt and output (HF / vLLM
+    # convention), presence / frequency over the output (OpenAI), per-token logprobs with the
+    # ``logprobs`` (0..8) most likely alternatives
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logprobs: Optional[int] = None
+
+    @property
+    def penalized(self) -> bool:
+        """Needs the per-sequence sampler state (token counts, prompt mask)."""
+        return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
+
+    @property
+    def extended(self) -> bool:
+        """Any of the extended sampler's parameters differs from its default."""
+        return self.penalized or self.logprobs is not None
 
 
 _ids = itertools.count(1)
@@ -55,6 +72,10 @@ class Sequence:
     request_id: str = ""
     seq_id: int = field(default_factory=lambda: next(_ids))
     output_ids: List[int] = field(default_factory=list)
+    # with ``params.logprobs`` set, in step with ``output_ids``: the token's logprob and the
+    # ``logprobs`` most likely ``(token id, logprob)`` pairs, descending
+    output_logprobs: List[float] = field(default_factory=list)
+    output_top_logprobs: List[List[Tuple[int, float]]] = field(default_factory=list)
     status: str = "waiting"  # waiting | running | finished
     finish_reason: Optional[str] = None
     arrival_time: float = field(default_factory=time.time)
@@ -70,6 +91,7 @@ class Sequence:
     # ever append, so they stay valid) and how many of its current blocks are indexed
     block_hashes: List[bytes] = field(default_factory=list, repr=False)
     indexed_blocks: int = 0
+    sampler_slot: int = -1  # row of the engine's sampler state (penalties), -1 = none held
 
     @property
     def all_ids(self) -> List[int]:
@@ -115,6 +137,9 @@ class ContinuousBatchScheduler:
         self.policy = policy
         self.waiting: Deque[Sequence] = deque()
         self.running: List[Sequence] = []
+        # called when a sequence leaves the running set (finished or preempted): the engine
+        # returns the sequence's sampler-state slot
+        self.on_release: Optional[Callable[[Sequence], None]] = None
 
     # ------------------------------------------------------------------ queue
     def add(self, seq: Sequence) -> None:
@@ -270,6 +295,8 @@ class ContinuousBatchScheduler:
             if table:
                 self.prefix_cache.insert(seq.all_ids, table, seq.num_computed, hashes=seq.block_hashes)
         self.kv.free_sequence(seq.seq_id)
+        if self.on_release is not None:
+            self.on_release(seq)
 
     def finish(self, seq: Sequence, reason: str) -> None:
         seq.status = "finished"

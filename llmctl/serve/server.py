@@ -39,6 +39,25 @@ class GenerationRequest(BaseModel):
     stop: Optional[Union[str, List[str]]] = None
     ignore_eos: bool = False
     model: Optional[str] = None
+    # the extended sampler: OpenAI's presence / frequency penalties (over the generated tokens),
+    # the HF-style repetition penalty (over prompt and generated tokens), per-token logprobs with
+    # the ``logprobs`` most likely alternatives
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    repetition_penalty: float = 1.0
+    logprobs: Optional[int] = None
+
+
+def validate_request(req: GenerationRequest) -> None:
+    """Range checks of the extended sampling fields (``ValueError``: answered with 400)."""
+    for name in ("presence_penalty", "frequency_penalty"):
+        v = getattr(req, name)
+        if not -2.0 <= v <= 2.0:
+            raise ValueError(f"{name} must be in [-2, 2], got {v}")
+    if not 0.0 < req.repetition_penalty <= 10.0:
+        raise ValueError(f"repetition_penalty must be in (0, 10], got {req.repetition_penalty}")
+    if req.logprobs is not None and not 0 <= req.logprobs <= 8:
+        raise ValueError(f"logprobs must be in 0..8, got {req.logprobs}")
 
 
 class GenerationResponse(BaseModel):
@@ -106,6 +125,10 @@ class InferenceServer:
         async def completions(req: GenerationRequest):
             if len(self.active_requests) >= self.max_concurrent:
                 raise HTTPException(status_code=503, detail="Server at capacity")
+            try:
+                validate_request(req)
+            except ValueError as e:
+                raise HTTPException(status_code=400, detail=str(e))
             if req.stream:
                 return StreamingResponse(self._stream(req), media_type="text/event-stream")
             try:
@@ -192,7 +215,17 @@ class InferenceServer:
 
         stop = [req.stop] if isinstance(req.stop, str) else (req.stop or [])
         return SamplingParams(max_tokens=max(1, req.max_tokens), temperature=req.temperature, top_p=req.top_p,
-                              top_k=req.top_k, stop=stop, ignore_eos=req.ignore_eos)
+                              top_k=req.top_k, stop=stop, ignore_eos=req.ignore_eos,
+                              repetition_penalty=req.repetition_penalty, presence_penalty=req.presence_penalty,
+                              frequency_penalty=req.frequency_penalty, logprobs=req.logprobs)
+
+    def _logprobs_payload(self, seq) -> Dict[str, Any]:
+        """``choices[0]["logprobs"]`` in the OpenAI completions shape: four lists, one entry per
+        generated token (``top_logprobs``: token text -> logprob of the most likely alternatives)."""
+        dec = self.engine.tokenizer.decode
+        return {"tokens": [dec([t]) for t in seq.output_ids], "token_ids": list(seq.output_ids),
+                "token_logprobs": list(seq.output_logprobs),
+                "top_logprobs": [{dec([t]): v for t, v in top} for top in seq.output_top_logprobs]}
 
     def _encode(self, prompt) -> List[int]:
         if isinstance(prompt, list):
@@ -229,9 +262,12 @@ class InferenceServer:
         self.obs.record_inference_request(lat, ttft=ttft, tpot=tpot)
         self.health.record_inference_request(lat, success=not str(seq.finish_reason).startswith("error"))
         usage = {"prompt_tokens": len(ids), "completion_tokens": n, "total_tokens": len(ids) + n}
+        choice = {"index": 0, "text": text, "finish_reason": seq.finish_reason}
+        if req.logprobs is not None:
+            choice["logprobs"] = self._logprobs_payload(seq)
         return GenerationResponse(id=rid, text=text, finish_reason=seq.finish_reason or "stop", usage=usage,
                                   created=int(t0), model=self.model_name,
-                                  choices=[{"index": 0, "text": text, "finish_reason": seq.finish_reason}],
+                                  choices=[choice],
                                   timing={"latency_s": lat, "ttft_s": ttft, "tpot_s": tpot})
 
     async def _stream(self, req: GenerationRequest):
@@ -240,7 +276,8 @@ class InferenceServer:
         rid = f"cmpl-{uuid.uuid4().hex[:16]}"
 
         def on_token(seq, tok):
-            loop.call_soon_threadsafe(q.put_nowait, ("tok", tok))
+            lp = seq.output_logprobs[-1] if seq.params.logprobs is not None else None
+            loop.call_soon_threadsafe(q.put_nowait, ("tok", (tok, lp)))
 
         def on_finish(seq):
             loop.call_soon_threadsafe(q.put_nowait, ("end", seq.finish_reason))
@@ -254,9 +291,12 @@ class InferenceServer:
             while True:
                 kind, val = await q.get()
                 if kind == "tok":
+                    val, lp = val
                     payload = {"id": rid, "object": "text_completion", "model": self.model_name,
                                "choices": [{"index": 0, "text": self.engine.tokenizer.decode([val]), "token": val,
                                             "finish_reason": None}]}
+                    if lp is not None:
+                        payload["choices"][0]["logprob"] = lp
                     yield f"data: {json.dumps(payload)}\n\n"
                 else:
                     payload = {"id": rid, "choices": [{"index": 0, "text": "", "finish_reason": val}]}

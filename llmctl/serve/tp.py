@@ -166,6 +166,15 @@ class TPInferenceEngine(InferenceEngine):
     def _publish(self, plan: Dict) -> Dict:
         return self._bcast(plan)
 
+    def add_request(self, prompt_ids, params, *args, **kw):
+        """Penalties and logprobs need the sampler state and its resets on every rank, which the
+        plan channel does not carry: such requests are refused at TP > 1."""
+        if self.tp_size > 1 and params.extended:
+            neutral = {"repetition_penalty": 1.0, "presence_penalty": 0.0, "frequency_penalty": 0.0, "logprobs": None}
+            bad = [k for k, v in neutral.items() if getattr(params, k) != v]
+            raise ValueError(f"{', '.join(bad)} not supported with tensor parallelism > 1 (TP = {self.tp_size})")
+        return super().add_request(prompt_ids, params, *args, **kw)
+
     @torch.inference_mode()
     def _decode_sample_exec(self, plan: Dict) -> torch.Tensor:
         toks = super()._decode_sample_exec(plan)
