@@ -20,10 +20,12 @@ def run_serving_benchmark(model: str = "gpt-7b", prompt_length: int = 2048, gen_
                           device: str = "auto", max_batch_tokens: Optional[int] = None, use_graphs: bool = True,
                           seed: int = 0, warmup: bool = True, scheduler: str = "dynamic",
                           kv_cache_dtype: str = "auto", weight_dtype: str = "auto",
-                          sampling: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+                          sampling: Optional[Dict[str, Any]] = None, num_loras: int = 0,
+                          lora_rank: int = 16) -> Dict[str, Any]:
     """``sampling``: extra ``SamplingParams`` fields of every request (penalties, logprobs), to
     time the extended sampler end to end; the warm-up uses them too, so its graphs are captured
-    before the timed run."""
+    before the timed run.  ``num_loras``: that many random LoRA adapters of rank ``lora_rank`` are
+    loaded and request ``i`` runs on adapter ``i % num_loras`` (warm-up included)."""
     import torch
 
     from llmctl.serve.engine import InferenceEngine
@@ -35,15 +37,28 @@ def run_serving_benchmark(model: str = "gpt-7b", prompt_length: int = 2048, gen_
                                                                    4096 if scheduler == "prefill_first" else 8192),
                           max_model_len=max_len,
                           use_graphs=use_graphs, seed=seed, scheduler=scheduler, kv_cache_dtype=kv_cache_dtype,
-                          weight_dtype=weight_dtype)
+                          weight_dtype=weight_dtype, max_loras=num_loras, max_lora_rank=lora_rank)
+    names = []
+    if num_loras > 0:
+        from llmctl.serve.lora import random_adapter
+
+        for i in range(num_loras):
+            eng.load_lora(f"lora{i}", random_adapter(eng.cfg, rank=lora_rank, seed=seed + i, std=0.01))
+            names.append(f"lora{i}")
     V = eng.cfg.vocab_size
     rng = random.Random(seed)
     extra = {k: v for k, v in (sampling or {}).items() if v is not None}
     params = SamplingParams(max_tokens=gen_length, temperature=0.0, ignore_eos=True, **extra)
+    req_params = [params if not names else SamplingParams(max_tokens=gen_length, temperature=0.0, ignore_eos=True,
+                                                          lora=names[i % len(names)], **extra)
+                  for i in range(num_requests)]
     if warmup:  # capture decode graphs, warm the allocator and the GEMM / attention paths of the
         # full-length prefill batches the timed run will form (first-use costs stay out of TTFT)
         eng.generate([[1] * 16 for _ in range(min(max_batch_size, num_requests))],
                      SamplingParams(max_tokens=4, temperature=0.0, ignore_eos=True, **extra))
+        if names:  # the LoRA graph family of the warm-up's bucket
+            eng.generate([[1] * 16 for _ in range(min(max_batch_size, num_requests))],
+                         SamplingParams(max_tokens=4, temperature=0.0, ignore_eos=True, lora=names[0], **extra))
         eng.generate([[2] * prompt_length for _ in range(min(max_batch_size, num_requests))],
                      SamplingParams(max_tokens=2, temperature=0.0, ignore_eos=True, **extra))
     prompts = [[rng.randrange(V) for _ in range(prompt_length)] for _ in range(num_requests)]
@@ -60,7 +75,7 @@ def run_serving_benchmark(model: str = "gpt-7b", prompt_length: int = 2048, gen_
         now = time.perf_counter() - start
         while pending and arrivals[pending[0]] <= now:
             i = pending.pop(0)
-            s = eng.add_request(prompts[i], params, request_id=str(i))
+            s = eng.add_request(prompts[i], req_params[i], request_id=str(i))
             s.arrival_time = time.time()
             seqs.append(s)
         if eng.scheduler.has_work():
@@ -89,6 +104,8 @@ def run_serving_benchmark(model: str = "gpt-7b", prompt_length: int = 2048, gen_
     }
     if extra:
         res["sampling"] = extra
+    if names:
+        res["num_loras"], res["lora_rank"] = num_loras, lora_rank
     eng.close()
     return res
 

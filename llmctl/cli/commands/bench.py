@@ -56,6 +56,8 @@ def e2e(
     frequency_penalty: float = typer.Option(0.0, help="Frequency penalty of every request (extended sampler)"),
     repetition_penalty: float = typer.Option(1.0, help="Repetition penalty of every request (extended sampler)"),
     logprobs: Optional[int] = typer.Option(None, help="Top logprobs per token, 0..8 (extended sampler)"),
+    num_loras: int = typer.Option(0, help="Random LoRA adapters to load; the requests are spread over them"),
+    lora_rank: int = typer.Option(16, help="Rank of those adapters (16, 32 or 64)"),
 ) -> None:
     """End-to-end serving benchmark (TTFT p50/p99, TPOT, tokens/s).
 
@@ -68,7 +70,7 @@ def e2e(
     res = run_serving_benchmark(model=model, prompt_length=prompt_length, gen_length=gen_length, qps=qps,
                                 num_requests=num_requests, max_batch_size=max_batch_size, device=device,
                                 scheduler=scheduler, max_batch_tokens=max_batch_tokens, kv_cache_dtype=kv_cache_dtype,
-                                weight_dtype=weight_dtype,
+                                weight_dtype=weight_dtype, num_loras=num_loras, lora_rank=lora_rank,
                                 sampling={"presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty,
                                           "repetition_penalty": repetition_penalty, "logprobs": logprobs})
     console.print_json(json.dumps(res))

@@ -9,7 +9,7 @@ Same flags (``--artifact --port --host --scheduler --max-batch-size --max-batch-
 from __future__ import annotations
 
 from pathlib import Path
-from typing import Optional
+from typing import List, Optional
 
 import typer
 from rich.console import Console
@@ -36,6 +36,10 @@ def start(
     weight_dtype: str = typer.Option("auto", help="Decode projection weights: auto (the model dtype), fp8 (OCP "
                                                   "e4m3fn, per-row scales) or int4 (group-128 scales, W4A16); "
                                                   "prefill keeps the model dtype"),
+    lora: Optional[List[str]] = typer.Option(None, "--lora", help="NAME=PATH of a LoRA adapter directory to serve "
+                                                                   "under NAME (repeatable)"),
+    max_loras: int = typer.Option(0, help="Resident LoRA adapter slots (at least the number of --lora)"),
+    max_lora_rank: int = typer.Option(16, help="Largest (fused) adapter rank: 16, 32 or 64"),
 ) -> None:
     """Start the inference server."""
     from llmctl.serve.server import create_inference_server
@@ -45,6 +49,16 @@ def start(
 
     if not p.exists() and artifact.lower() not in ALIASES:
         console.print(f"[red]Artifact not found: {artifact}[/red]")
+        raise typer.Exit(1)
+    loras = {}
+    for item in lora or []:
+        name, sep, path = item.partition("=")
+        if not sep or not name or not Path(path).is_dir():
+            console.print(f"[red]--lora takes NAME=PATH of an adapter directory, got {item!r}[/red]")
+            raise typer.Exit(1)
+        loras[name] = path
+    if loras and tensor_parallel > 1:
+        console.print("[red]LoRA adapters not supported with tensor parallelism > 1[/red]")
         raise typer.Exit(1)
     console.print("[blue]Starting inference server...[/blue]")
     console.print(f"[yellow]Artifact: {artifact}[/yellow]  [yellow]Endpoint: http://{host}:{port}[/yellow]")
@@ -70,7 +84,8 @@ def start(
                                      max_batch_tokens=max_batch_tokens, max_concurrent=max_concurrent,
                                      scheduler=scheduler, device=device, kv_cache_fraction=kv_cache_fraction,
                                      block_size=block_size, use_graphs=cuda_graphs, tensor_parallel=tensor_parallel,
-                                     kv_cache_dtype=kv_cache_dtype, weight_dtype=weight_dtype)
+                                     kv_cache_dtype=kv_cache_dtype, weight_dtype=weight_dtype, loras=loras,
+                                     max_loras=max_loras, max_lora_rank=max_lora_rank)
     try:
         server.run()
     except KeyboardInterrupt:
@@ -93,4 +108,4 @@ def main(
         raise typer.Exit(1)
     start(artifact=artifact, port=port, host=host, scheduler="dynamic", max_batch_size=8, max_batch_tokens=8192,
           max_concurrent=128, device=device, kv_cache_fraction=0.85, block_size=16, cuda_graphs=True,
-          tensor_parallel=1, kv_cache_dtype="auto", weight_dtype="auto")
+          tensor_parallel=1, kv_cache_dtype="auto", weight_dtype="auto", lora=None, max_loras=0, max_lora_rank=16)

@@ -27,6 +27,8 @@ from .functional import (
     layernorm,
     linear_acc_,
     linear_rowscale,
+    lora_delta,
+    LoRARows,
     MoEExpertTable,
     moe_decode_down_add_rmsnorm,
     moe_decode_ok,
@@ -57,5 +59,5 @@ __all__ = [
     "paged_prefill_attention", "prefill_work_list", "attn_merge_",
     "rmsnorm", "rope_qkv", "rope_flash_attention", "rope_qkv_cache", "sample", "sample_ext", "sampler_state_reset", "swiglu", "transpose_", "up_swiglu",
     "rms_rstd", "linear_rowscale", "up_swiglu_rowscale", "linear_acc_",
-    "MoEExpertTable", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",
+    "LoRARows", "lora_delta", "MoEExpertTable", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",
 ]

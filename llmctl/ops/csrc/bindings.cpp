@@ -49,12 +49,14 @@ TORCH_LIBRARY(llmctl, m) {
   m.def("paged_attention_decode(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor context_lens, float scale) -> Tensor");
   m.def("skinny_linear(Tensor x, Tensor w, Tensor? bias) -> Tensor");
   m.def("skinny_linear_cfg(Tensor x, Tensor w, Tensor? bias, int config) -> Tensor");
-  m.def("decode_qkv_rope_cache(Tensor x, Tensor w, Tensor? bias, Tensor cos, Tensor sin, int nq, int nkv, Tensor positions, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slots, Tensor? w_scale=None) -> Tensor");
-  m.def("decode_up_swiglu(Tensor x, Tensor w, Tensor? bias, Tensor? w_scale=None) -> Tensor");
+  m.def("decode_qkv_rope_cache(Tensor x, Tensor w, Tensor? bias, Tensor cos, Tensor sin, int nq, int nkv, Tensor positions, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slots, Tensor? w_scale=None, Tensor? lora_idx=None, Tensor? lora_a=None, Tensor? lora_b=None, Tensor? lora_scale=None) -> Tensor");
+  m.def("decode_up_swiglu(Tensor x, Tensor w, Tensor? bias, Tensor? w_scale=None, Tensor? lora_idx=None, Tensor? lora_a=None, Tensor? lora_b=None, Tensor? lora_scale=None) -> Tensor");
   m.def("decode_linear_partials(Tensor x, Tensor w, Tensor? w_scale=None) -> Tensor");
-  m.def("decode_linear_add_rmsnorm(Tensor x, Tensor w, Tensor? bias, Tensor residual, Tensor norm_w, float eps, Tensor? w_scale=None) -> (Tensor, Tensor)");
-  m.def("decode_linear_fp8(Tensor x, Tensor w, Tensor w_scale, Tensor? bias) -> Tensor");
-  m.def("decode_linear_int4(Tensor x, Tensor qweight, Tensor scale, Tensor? bias) -> Tensor");
+  m.def("decode_linear_add_rmsnorm(Tensor x, Tensor w, Tensor? bias, Tensor residual, Tensor norm_w, float eps, Tensor? w_scale=None, Tensor? lora_idx=None, Tensor? lora_a=None, Tensor? lora_b=None, Tensor? lora_scale=None) -> (Tensor, Tensor)");
+  m.def("decode_linear_fp8(Tensor x, Tensor w, Tensor w_scale, Tensor? bias, Tensor? lora_idx=None, Tensor? lora_a=None, Tensor? lora_b=None, Tensor? lora_scale=None) -> Tensor");
+  m.def("decode_linear_int4(Tensor x, Tensor qweight, Tensor scale, Tensor? bias, Tensor? lora_idx=None, Tensor? lora_a=None, Tensor? lora_b=None, Tensor? lora_scale=None) -> Tensor");
+  // per-row LoRA adapters (lora_decode.hip): delta fp32 [M, N]; lora_idx int32 [M], slot or -1
+  m.def("lora_delta(Tensor x, Tensor lora_idx, Tensor lora_a, Tensor lora_b, Tensor lora_scale) -> Tensor");
   // routed-expert decode MLP (moe_decode.hip); *_ptrs: int64 [E] device table of expert weight pointers
   m.def("moe_route(Tensor x, Tensor w_router, int k) -> (Tensor, Tensor)");
   m.def("moe_decode_up_swiglu(Tensor x, Tensor up_ptrs, Tensor topi, int E, int F) -> Tensor");

@@ -764,6 +764,10 @@ at::Tensor skinny_linear(const at::Tensor& x, const at::Tensor& w, const c10::op
   return skinny_linear_cfg(x, w, bias, 0);
 }
 
+// lora_decode.hip: the per-row adapter delta [M, N] fp32 into ``out``
+void lora_delta_into(const at::Tensor& x, const at::Tensor& idx, const at::Tensor& A, const at::Tensor& B,
+                     const at::Tensor& scale, float* out, int64_t N, const char* who);
+
 // ---- fused decode projections (v2 GEMM partials + epilogue finalize), M <= 16 ------------------
 namespace {
 constexpr int kFusedKC = 1024;  // K chunk of the fused projections (config 23's)
@@ -793,12 +797,13 @@ bool w_int4(const at::Tensor& w) { return w.scalar_type() == at::kByte; }
 
 // x W^T as fp32 K-chunk partials ws [KS][M][N]; returns KS.  fp8 W: w_scale [N] fp32 row scales;
 // int4 W (uint8 [N, K / 2]): w_scale [N, K / 128] fp32 group scales.
+// ``extra``: slices allocated past the KS the GEMM writes (the LoRA delta's).
 int decode_partials(const at::Tensor& x, const at::Tensor& w, at::Tensor& ws,
-                    const c10::optional<at::Tensor>& w_scale = c10::nullopt) {
+                    const c10::optional<at::Tensor>& w_scale = c10::nullopt, int extra = 0) {
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   const int KC = std::min(kFusedKC, K);
   const int KS = (K + KC - 1) / KC;
-  ws = at::empty({(long)KS * M * N}, x.options().dtype(at::kFloat));
+  ws = at::empty({(long)(KS + extra) * M * N}, x.options().dtype(at::kFloat));
   if (w_fp8(w)) {
     // (two 16-row tiles per wave, and K chunks of 512 / 2048, measured 3-6 % slower in the decode
     // step: profiles/decode_w8_r5.txt)
@@ -834,6 +839,26 @@ int decode_partials(const at::Tensor& x, const at::Tensor& w, at::Tensor& ws,
                        bf_ptr(x), bf_ptr(w), nullptr, nullptr, ws.data_ptr<float>(), M, N, K, KC);
   return KS;
 }
+
+using OptT = c10::optional<at::Tensor>;
+bool has(const OptT& t) { return t.has_value() && t->defined(); }
+
+// The partials of a projection that may carry per-row LoRA adapters: with ``lora_idx`` given, the
+// adapter delta (lora_decode.hip) is one more fp32 slice, ws [KS + 1][M][N], which every finalize
+// kernel sums with the K chunks before its epilogue.  Returns the slice count for the finalize.
+int decode_partials_lora(const at::Tensor& x, const at::Tensor& w, at::Tensor& ws, const OptT& w_scale,
+                         const OptT& lora_idx, const OptT& lora_a, const OptT& lora_b, const OptT& lora_scale,
+                         const char* who) {
+  if (!has(lora_idx)) {
+    LLMCTL_CHECK(!has(lora_a) && !has(lora_b) && !has(lora_scale), who, ": LoRA tensors given without lora_idx");
+    return decode_partials(x, w, ws, w_scale);
+  }
+  LLMCTL_CHECK(has(lora_a) && has(lora_b) && has(lora_scale), who, ": lora_idx needs lora_a, lora_b and lora_scale");
+  const int M = x.size(0), N = w.size(0);
+  const int KS = decode_partials(x, w, ws, w_scale, 1);
+  lora_delta_into(x, *lora_idx, *lora_a, *lora_b, *lora_scale, ws.data_ptr<float>() + (long)KS * M * N, N, who);
+  return KS + 1;
+}
 }  // namespace
 
 // x W^T as fp32 K-chunk partials [KS, M, N] (the fused decode attention sums them itself)
@@ -850,7 +875,8 @@ at::Tensor decode_linear_partials(const at::Tensor& x, const at::Tensor& w, cons
 at::Tensor decode_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
                                  const at::Tensor& cosT, const at::Tensor& sinT, int64_t nq, int64_t nkv,
                                  const at::Tensor& positions, at::Tensor& k_cache, at::Tensor& v_cache,
-                                 const at::Tensor& slots, const c10::optional<at::Tensor>& w_scale) {
+                                 const at::Tensor& slots, const c10::optional<at::Tensor>& w_scale,
+    const OptT& lora_idx, const OptT& lora_a, const OptT& lora_b, const OptT& lora_scale) {
   check_decode_operands(x, w, bias, "decode_qkv_rope_cache");
   const int M = x.size(0), N = w.size(0);
   const int NH = nq + 2 * nkv;
@@ -871,7 +897,7 @@ at::Tensor decode_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w, const
                "decode_qkv_rope_cache: k/v cache contiguous bf16 or fp8 (e4m3fn) [blocks, block_size, Hkv, D]");
   const c10::DeviceGuard guard(x.device());
   at::Tensor ws;
-  const int KS = decode_partials(x, w, ws, w_scale);
+  const int KS = decode_partials_lora(x, w, ws, w_scale, lora_idx, lora_a, lora_b, lora_scale, "decode_qkv_rope_cache");
   auto q = at::empty({M, nq, D}, x.options());
   const long total = (long)M * NH * (D / 16);
   hipLaunchKernelGGL(decode_fin_rope_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream(),
@@ -883,12 +909,13 @@ at::Tensor decode_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w, const
 
 // act [M, F] = silu(g) * u of the gate/up projection gu = x W^T + b  ([M, 2F], gate first)
 at::Tensor decode_up_swiglu(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
-                            const c10::optional<at::Tensor>& w_scale) {
+                            const c10::optional<at::Tensor>& w_scale,
+    const OptT& lora_idx, const OptT& lora_a, const OptT& lora_b, const OptT& lora_scale) {
   check_decode_operands(x, w, bias, "decode_up_swiglu");
   const int M = x.size(0), N = w.size(0), F = N / 2;
   const c10::DeviceGuard guard(x.device());
   at::Tensor ws;
-  const int KS = decode_partials(x, w, ws, w_scale);
+  const int KS = decode_partials_lora(x, w, ws, w_scale, lora_idx, lora_a, lora_b, lora_scale, "decode_up_swiglu");
   auto act = at::empty({M, F}, x.options());
   const long n4 = (long)M * F / 4;
   hipLaunchKernelGGL(decode_fin_swiglu_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream(),
@@ -900,7 +927,8 @@ at::Tensor decode_up_swiglu(const at::Tensor& x, const at::Tensor& w, const c10:
 std::tuple<at::Tensor, at::Tensor> decode_linear_add_rmsnorm(const at::Tensor& x, const at::Tensor& w,
                                                              const c10::optional<at::Tensor>& bias,
                                                              const at::Tensor& res, const at::Tensor& norm_w,
-                                                             double eps, const c10::optional<at::Tensor>& w_scale) {
+                                                             double eps, const c10::optional<at::Tensor>& w_scale,
+    const OptT& lora_idx, const OptT& lora_a, const OptT& lora_b, const OptT& lora_scale) {
   check_decode_operands(x, w, bias, "decode_linear_add_rmsnorm");
   const int M = x.size(0), N = w.size(0);
   LLMCTL_CHECK(res.is_contiguous() && res.scalar_type() == at::kBFloat16 && res.dim() == 2 && res.size(0) == M &&
@@ -911,7 +939,7 @@ std::tuple<at::Tensor, at::Tensor> decode_linear_add_rmsnorm(const at::Tensor& x
   LLMCTL_CHECK(N <= 16384, "decode_linear_add_rmsnorm: N <= 16384 (row staged in LDS)");
   const c10::DeviceGuard guard(x.device());
   at::Tensor ws;
-  const int KS = decode_partials(x, w, ws, w_scale);
+  const int KS = decode_partials_lora(x, w, ws, w_scale, lora_idx, lora_a, lora_b, lora_scale, "decode_linear_add_rmsnorm");
   auto y = at::empty({M, N}, x.options());
   auto res_out = at::empty({M, N}, x.options());
   hipLaunchKernelGGL(decode_fin_add_rmsnorm_kernel, dim3(M), dim3(1024), (size_t)N * 4, stream(), ws.data_ptr<float>(),
@@ -921,13 +949,14 @@ std::tuple<at::Tensor, at::Tensor> decode_linear_add_rmsnorm(const at::Tensor& x
 
 // y [M, N] = x W^T (+ b) with fp8 (e4m3fn) W and fp32 row scales: partials + decode_finalize_kernel
 at::Tensor decode_linear_fp8(const at::Tensor& x, const at::Tensor& w, const at::Tensor& w_scale,
-                             const c10::optional<at::Tensor>& bias) {
+                             const c10::optional<at::Tensor>& bias,
+    const OptT& lora_idx, const OptT& lora_a, const OptT& lora_b, const OptT& lora_scale) {
   check_decode_operands(x, w, bias, "decode_linear_fp8");
   LLMCTL_CHECK(w_fp8(w), "decode_linear_fp8: fp8 (e4m3fn) weights");
   const int M = x.size(0), N = w.size(0);
   const c10::DeviceGuard guard(x.device());
   at::Tensor ws;
-  const int KS = decode_partials(x, w, ws, w_scale);
+  const int KS = decode_partials_lora(x, w, ws, w_scale, lora_idx, lora_a, lora_b, lora_scale, "decode_linear_fp8");
   auto y = at::empty({M, N}, x.options());
   const long n4 = (long)M * N / 4;
   hipLaunchKernelGGL(decode_finalize_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream(),
@@ -937,13 +966,14 @@ at::Tensor decode_linear_fp8(const at::Tensor& x, const at::Tensor& w, const at:
 
 // y [M, N] = x W^T (+ b) with int4 W (uint8 [N, K / 2], two k per byte) and fp32 group-128 scales [N, K / 128]
 at::Tensor decode_linear_int4(const at::Tensor& x, const at::Tensor& w, const at::Tensor& w_scale,
-                              const c10::optional<at::Tensor>& bias) {
+                              const c10::optional<at::Tensor>& bias,
+    const OptT& lora_idx, const OptT& lora_a, const OptT& lora_b, const OptT& lora_scale) {
   check_decode_operands(x, w, bias, "decode_linear_int4");
   LLMCTL_CHECK(w_int4(w), "decode_linear_int4: packed int4 (uint8) weights");
   const int M = x.size(0), N = w.size(0);
   const c10::DeviceGuard guard(x.device());
   at::Tensor ws;
-  const int KS = decode_partials(x, w, ws, w_scale);
+  const int KS = decode_partials_lora(x, w, ws, w_scale, lora_idx, lora_a, lora_b, lora_scale, "decode_linear_int4");
   auto y = at::empty({M, N}, x.options());
   const long n4 = (long)M * N / 4;
   hipLaunchKernelGGL(decode_finalize_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream(),

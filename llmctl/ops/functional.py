@@ -416,11 +416,59 @@ def paged_prefill_attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, s
     return ref.paged_prefill_attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, scale)
 
 
+class LoRARows:
+    """Per-row LoRA adapters of one projection, as the decode ops take them (``lora=``): ``idx`` int32
+    ``[M]`` (an adapter slot per token row, -1 = none) and the projection's resident stacked adapters
+    ``A [slots, R, K]``, ``B [slots, N, R]`` (bf16 on the GPU) and ``scale [slots]`` fp32."""
+
+    __slots__ = ("idx", "A", "B", "scale")
+
+    def __init__(self, idx, A, B, scale):
+        self.idx, self.A, self.B, self.scale = idx, A, B, scale
+
+    def args(self):
+        return self.idx, self.A, self.B, self.scale
+
+    def rows(self, idx):
+        """The same adapters under another row selection."""
+        return LoRARows(idx, self.A, self.B, self.scale)
+
+
+def lora_delta(x, lora_idx, lora_a, lora_b, lora_scale):
+    """fp32 ``[M, N]`` LoRA delta of every row under its own adapter (``csrc/lora_decode.hip``):
+    ``scale[s] * (x[m] @ A[s]^T) @ B[s]^T`` with ``s = lora_idx[m]``, zeros where ``s < 0``."""
+    if use_native(x):
+        return native().lora_delta(x.contiguous(), lora_idx, lora_a, lora_b, lora_scale)
+    return ref.lora_delta(x, lora_idx, lora_a, lora_b, lora_scale)
+
+
+def _lora_args(lora):
+    return (None, None, None, None) if lora is None else lora.args()
+
+
+def _add_lora(y, x, w, b, lora):
+    """The unfused form of a projection with adapters.  ``y`` is the base projection as computed
+    without adapters (rows without an adapter keep it, bit for bit); adapter rows become
+    ``x w^T (+ b) + delta`` summed in fp32 and rounded once, as the fused decode projections round
+    them -- the base product is taken again with an fp32 result (a library GEMM: this form runs where
+    the fused kernels do not, at the price of streaming ``w`` twice).  fp32 ``y``: a plain add."""
+    if lora is None:
+        return y
+    d = lora_delta(x, *lora.args())
+    if y.dtype == torch.float32:
+        return y + d
+    base = torch.mm(x, w.t(), out_dtype=torch.float32)
+    if b is not None:
+        base = base + b.float()
+    return torch.where((lora.idx >= 0).unsqueeze(1), (base + d).to(y.dtype), y)
+
+
 SKINNY_CONFIGS: dict = {}  # (M, N, K) -> tuned config (0 = hipBLASLt), from a tuning cache
 
 
-def decode_linear(x, w, b=None):
-    """``x @ w^T (+ b)`` for decode-shaped inputs: the weight-streaming MFMA kernels
+def decode_linear(x, w, b=None, lora: Optional[LoRARows] = None):
+    """``x @ w^T (+ b)`` for decode-shaped inputs (``lora``: per-row adapters, their delta added in
+    fp32, :func:`lora_delta`): the weight-streaming MFMA kernels
     (``csrc/skinny_gemm.hip``) where they beat hipBLASLt on uncached weights
     (``profiles/skinny_sweep_r2*.jsonl``): every projection up to 16 tokens (at 16 tokens the
     LDS-staged v2 kernel: QKV 3.78 vs 3.55 TB/s, up 3.89 vs 3.35, down 3.16 vs 2.07) and the
@@ -428,6 +476,8 @@ def decode_linear(x, w, b=None):
     does the vocabulary projection (out features >= 16384) from 8 tokens (GPT-7B LM head at 16
     tokens: 59.7 vs 68.5 us, ``profiles/decode_gemm_nt_r5.txt``).
     Knob ``skinny_gemm``: ``off`` / ``all`` force the library / kernel path (A/B)."""
+    if lora is not None:
+        return _add_lora(decode_linear(x, w, b), x, w, b, lora)
     from llmctl.exec.linear import forward_linear
 
     mode = knobs().skinny_gemm
@@ -457,22 +507,22 @@ def _dequant(w, w_scale, dtype):
     return (w.float() * w_scale.float().unsqueeze(1)).to(dtype)
 
 
-def decode_linear_fp8(x, w, w_scale, b=None):
+def decode_linear_fp8(x, w, w_scale, b=None, lora: Optional[LoRARows] = None):
     """``x @ (w * w_scale[:, None])^T (+ b)`` for decode-shaped inputs with fp8 (OCP e4m3fn)
     weights and fp32 row scales (W8A16: ``csrc/skinny_gemm.hip``'s fp8 weight stream, half the
     bytes of the bf16 one)."""
     if decode_fused_ok(x, w):
-        return native().decode_linear_fp8(x, w, w_scale, b)
-    return decode_linear(x, _dequant(w, w_scale, x.dtype), b)
+        return native().decode_linear_fp8(x, w, w_scale, b, *_lora_args(lora))
+    return decode_linear(x, _dequant(w, w_scale, x.dtype), b, lora)
 
 
-def decode_linear_int4(x, qweight, scale, b=None):
+def decode_linear_int4(x, qweight, scale, b=None, lora: Optional[LoRARows] = None):
     """``x @ dequant(qweight, scale)^T (+ b)`` for decode-shaped inputs with group-128 int4 weights
     (W4A16, ``quantizers.quantize_int4_g128``: uint8 ``[N, K/2]`` + fp32 scales ``[N, K/128]``;
     ``csrc/skinny_gemm.hip``'s int4 weight stream, 4.25 bits per weight)."""
     if decode_fused_ok(x, qweight):
-        return native().decode_linear_int4(x, qweight, scale, b)
-    return decode_linear(x, _dequant(qweight, scale, x.dtype), b)
+        return native().decode_linear_int4(x, qweight, scale, b, *_lora_args(lora))
+    return decode_linear(x, _dequant(qweight, scale, x.dtype), b, lora)
 
 
 def decode_fused_ok(x, w) -> bool:
@@ -488,26 +538,26 @@ def decode_fused_ok(x, w) -> bool:
 
 
 def decode_qkv_rope_cache(x, w, b, cos, sin, nq: int, nkv: int, positions, k_cache, v_cache, slots,
-                          w_scale=None):
+                          w_scale=None, lora: Optional[LoRARows] = None):
     """Decode QKV projection + RoPE + paged-cache write of K/V in one finalize pass; returns
     ``q [T, nq, D]``.  Same result as ``rope_qkv_cache(decode_linear(x, w, b), ...)[0]``.
     ``w_scale``: fp32 row scales of an fp8 (e4m3fn) ``w``, or fp32 group-128 scales of a packed
     int4 one."""
     if decode_fused_ok(x, w):
         return native().decode_qkv_rope_cache(x, w, b, cos, sin, nq, nkv, positions.to(torch.int32).contiguous(),
-                                              k_cache, v_cache, slots, w_scale)
-    return rope_qkv_cache(decode_linear(x, _dequant(w, w_scale, x.dtype), b), cos, sin, nq, nkv, 0, positions,
+                                              k_cache, v_cache, slots, w_scale, *_lora_args(lora))
+    return rope_qkv_cache(decode_linear(x, _dequant(w, w_scale, x.dtype), b, lora), cos, sin, nq, nkv, 0, positions,
                           k_cache, v_cache, slots)[0]
 
 
 def decode_attention_qkv(x, w, b, cos, sin, nq: int, nkv: int, positions, k_cache, v_cache, slots, block_tables,
-                         ctx_lens, scale: Optional[float] = None, w_scale=None):
+                         ctx_lens, scale: Optional[float] = None, w_scale=None, lora: Optional[LoRARows] = None):
     """Decode QKV projection -> RoPE -> paged-cache write (one finalize pass) -> paged attention.
     (Round 2's variant that summed the projection partials inside the attention kernel measured
     0.1-0.2 ms slower per 16 x 2k GPT-7B step, profiles/serve_r2_session6.txt, and was retired.)"""
     D = w.shape[0] // (nq + 2 * nkv)
     scale = scale if scale is not None else D ** -0.5
-    q = decode_qkv_rope_cache(x, w, b, cos, sin, nq, nkv, positions, k_cache, v_cache, slots, w_scale)
+    q = decode_qkv_rope_cache(x, w, b, cos, sin, nq, nkv, positions, k_cache, v_cache, slots, w_scale, lora)
     return paged_attention_decode(q, k_cache, v_cache, block_tables, ctx_lens, scale)
 
 
@@ -532,12 +582,12 @@ def up_swiglu(x, w, b=None):
     return swiglu(forward_linear(x, w, b))
 
 
-def decode_up_swiglu(x, w, b=None, w_scale=None):
+def decode_up_swiglu(x, w, b=None, w_scale=None, lora: Optional[LoRARows] = None):
     """Decode gate/up projection with SwiGLU in its finalize pass: ``silu(g) * u`` of
     ``x @ w^T (+ b)`` (gate = first half of the out features)."""
     if decode_fused_ok(x, w):
-        return native().decode_up_swiglu(x, w, b, w_scale)
-    return swiglu(decode_linear(x, _dequant(w, w_scale, x.dtype), b))
+        return native().decode_up_swiglu(x, w, b, w_scale, *_lora_args(lora))
+    return swiglu(decode_linear(x, _dequant(w, w_scale, x.dtype), b, lora))
 
 
 # ----------------------------------------------------------- prefill with the RMSNorm folded in
@@ -594,12 +644,12 @@ def linear_acc_(x, w, out):
     return out.addmm_(x, w.t())
 
 
-def decode_linear_add_rmsnorm(x, w, b, residual, norm_w, eps: float, w_scale=None):
+def decode_linear_add_rmsnorm(x, w, b, residual, norm_w, eps: float, w_scale=None, lora: Optional[LoRARows] = None):
     """Decode row projection + residual add + RMSNorm in one finalize pass:
     ``(rmsnorm(y + residual) * norm_w, y + residual)`` with ``y = x @ w^T (+ b)``."""
     if decode_fused_ok(x, w) and w.shape[0] <= 16384:
-        return native().decode_linear_add_rmsnorm(x, w, b, residual, norm_w, eps, w_scale)
-    y = decode_linear(x, _dequant(w, w_scale, x.dtype), b)
+        return native().decode_linear_add_rmsnorm(x, w, b, residual, norm_w, eps, w_scale, *_lora_args(lora))
+    y = decode_linear(x, _dequant(w, w_scale, x.dtype), b, lora)
     return add_rmsnorm(y, residual, norm_w, eps)
 
 

@@ -534,3 +534,20 @@ def moe_decode_mlp(x, experts_up, experts_down, topi, topw, residual, norm_w, ep
     MLPs of the routed copies, weighted combine, residual add and RMSNorm -> ``(xn, res_out)``."""
     act = moe_decode_up_swiglu(x, experts_up, topi)
     return moe_decode_down_add_rmsnorm(act, experts_down, topi, topw, residual, norm_w, eps)
+
+
+# ----------------------------------------------------------------------------- per-row LoRA adapters
+def lora_delta(x, lora_idx, lora_a, lora_b, lora_scale) -> torch.Tensor:
+    """``delta[m, n] = scale[s] * sum_j (sum_k x[m, k] A[s, j, k]) B[s, n, j]`` with ``s = lora_idx[m]``;
+    rows with ``s < 0`` are exact zeros.  ``lora_a [slots, R, K]``, ``lora_b [slots, N, R]``,
+    ``lora_scale [slots]``.  fp32 throughout, the inner sum not rounded (fp64 inputs: fp64)."""
+    dt = torch.float64 if x.dtype == torch.float64 else torch.float32
+    M, N = x.shape[0], lora_b.shape[1]
+    out = torch.zeros(M, N, dtype=dt, device=x.device)
+    idx = lora_idx.long()
+    for s in range(lora_a.shape[0]):
+        rows = (idx == s).nonzero().flatten()
+        if rows.numel():
+            t = x[rows].to(dt) @ lora_a[s].to(dt).t()
+            out[rows] = lora_scale[s].to(dt) * (t @ lora_b[s].to(dt).t())
+    return out

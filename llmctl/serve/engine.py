@@ -54,7 +54,8 @@ class InferenceEngine:
                  block_size: int = 16, num_kv_blocks: Optional[int] = None, scheduler: str = "dynamic",
                  use_graphs: bool = True, seed: int = 0, pc=None, prefix_caching: bool = True,
                  tuning_cache: Optional[str] = None, perf_knobs: Optional[Dict] = None,
-                 kv_cache_dtype: str = "auto", weight_dtype: str = "auto"):
+                 kv_cache_dtype: str = "auto", weight_dtype: str = "auto", max_loras: int = 0,
+                 max_lora_rank: int = 16):
         from llmctl.config import knobs as perf
 
         self.knobs = perf.configure(perf_knobs)  # defaults + perf_knobs + LLMCTL_KNOBS
@@ -107,6 +108,15 @@ class InferenceEngine:
         # columns ((H + 2 kv) D + 2 F) H bf16 per layer, made before the KV cache is sized
         self._nf: Optional[List[Tuple[torch.Tensor, torch.Tensor]]] = (
             self._fold_norm_weights() if self.knobs.prefill_norm_fold else None)
+        # LoRA adapters (llmctl/serve/lora.py): ``max_loras`` resident slots of rank ``max_lora_rank``
+        # per (layer, projection), made before the KV cache is sized; 0 = none, nothing changes
+        self.max_loras, self.max_lora_rank = int(max_loras), int(max_lora_rank)
+        self._lora: Optional[List[Dict[str, Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]]] = None
+        self._lora_slots: Dict[str, int] = {}  # adapter name -> slot
+        self._lora_salt: Dict[str, bytes] = {}  # adapter name -> prefix-cache salt of this load
+        self._lora_scale: Dict[int, float] = {}  # slot -> scale (host copy, for the eager prefill)
+        if self.max_loras > 0:
+            self._lora = self._alloc_lora()
         # KV cache element: the model dtype ("auto"), or OCP fp8 e4m3fn ("fp8": half the bytes per
         # token, so twice the blocks and half the decode attention's HBM stream; saturating at +-448)
         if kv_cache_dtype in ("auto", "model", "bf16", "bfloat16"):
@@ -150,6 +160,9 @@ class InferenceEngine:
         # [max_batch_size, V]) lives on the device -- an asynchronous step is launched before the
         # previous step's tokens reach the host -- and is allocated on first need.
         self._graphs_ext: Dict[int, Tuple[torch.cuda.CUDAGraph, Dict[str, torch.Tensor]]] = {}
+        # batches with an adapter row replay a third family, keyed (bucket, extended): the same body
+        # with every projection's ``ops.LoRARows`` passed down and a static per-row ``lora_idx``
+        self._graphs_lora: Dict[Tuple[int, bool], Tuple[torch.cuda.CUDAGraph, Dict[str, torch.Tensor]]] = {}
         self._sampler_state: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
         self._sampler_free: List[int] = []
         self._ext_step: Optional[Dict[str, np.ndarray]] = None  # the extended fields of the step being launched
@@ -216,7 +229,9 @@ class InferenceEngine:
         kernels' row limit run eagerly through the ``MoEMLP`` module, which syncs with the host.)"""
         return self.use_graphs and (not self.cfg.is_moe or self._moe_fused(self._bucket(n)))
 
-    def _norm_fold_ok(self, T: int) -> bool:
+    def _norm_fold_ok(self, T: int, lora=None) -> bool:
+        if lora is not None:  # a step with adapter rows takes the unfolded layers
+            return False
         return self._nf is not None and self.knobs.prefill_norm_fold and T > 0 and T % 256 == 0
 
     def _prefill_layers_folded(self, x, pos, slots, fa, doc, bt, cu, ctx, work):
@@ -289,10 +304,39 @@ class InferenceEngine:
             return (ops.layernorm(x, w, b, eps) if b is not None else ops.rmsnorm(x, w, eps)), x
         return ops.add_layernorm(x, res, w, b, eps) if b is not None else ops.add_rmsnorm(x, res, w, eps)
 
-    def _qkv(self, layer, xn, positions, seq_len, kc, vc, slots):
+    def _lin(self, x, w, b, li: int, name: str, sel):
+        """``ops.decode_linear`` of projection ``name`` of layer ``li`` with the step's adapters.
+        ``sel``: None (no adapter row in the step), an int32 device tensor (a slot or -1 per row:
+        ``ops.lora_delta``, the decode form) or a host list of ``(row0, row1, slot)`` segments (the
+        eager prefill / mixed step, whose chunks are contiguous row ranges: per segment
+        ``y = x W^T + scale (x A^T) B^T`` with library GEMMs, in fp32 before the rounding)."""
+        if sel is None:
+            return ops.decode_linear(x, w, b)
+        A, B, sc = self._lora[li][name]
+        if isinstance(sel, torch.Tensor):
+            return ops.decode_linear(x, w, b, lora=ops.LoRARows(sel, A, B, sc))
+        # rows outside every segment keep the projection exactly as a step without adapters computes it
+        covered = sum(r1 - r0 for r0, r1, _ in sel) == x.shape[0]
+        y = (torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device) if covered and x.dtype != torch.float32
+             else ops.decode_linear(x, w, b))
+        for r0, r1, slot in sel:
+            xs = x[r0:r1]
+            d = self._lora_scale[slot] * ((xs.float() @ A[slot].float().t()) @ B[slot].float().t())
+            if y.dtype == torch.float32:
+                y[r0:r1] += d
+                continue
+            # the segment's product again with an fp32 result: sum + delta rounded once, like the
+            # fused decode projections (a resumed sequence's prefill continues its decode steps)
+            base = torch.mm(xs, w.t(), out_dtype=torch.float32)
+            if b is not None:
+                base = base + b.float()
+            y[r0:r1] = (base + d).to(y.dtype)
+        return y
+
+    def _qkv(self, layer, xn, positions, seq_len, kc, vc, slots, li: int = 0, sel=None):
         """QKV projection, RoPE and the paged-cache write of this step's K/V rows (one fused
         pass with RoPE)."""
-        qkv = ops.decode_linear(xn, layer.wqkv, layer.bqkv)
+        qkv = self._lin(xn, layer.wqkv, layer.bqkv, li, "wqkv", sel)
         if self.rope is not None:
             return ops.rope_qkv_cache(qkv, self.rope[0], self.rope[1], layer.nq, layer.nkv, seq_len, positions,
                                       kc, vc, slots)
@@ -303,16 +347,18 @@ class InferenceEngine:
         ops.kv_cache_write(k, v, kc, vc, slots)
         return q, k, v
 
-    def _mlp(self, layer, xn):
+    def _mlp(self, layer, xn, li: int = 0, sel=None):
         if layer.moe is not None:  # routed experts (host-side split sizes: eager, no graphs)
             return layer.moe(xn)
         if self.cfg.gated_mlp:
             # prefill-sized (T % 256 == 0): the SwiGLU rides on the gate/up GEMM's epilogue
-            act = (ops.up_swiglu(xn, layer.w_up, layer.b_up) if xn.shape[0] >= 256 and xn.shape[0] % 256 == 0
-                   else ops.swiglu(ops.decode_linear(xn, layer.w_up, layer.b_up)))
-            out = ops.decode_linear(act, layer.w_down)
+            act = (ops.up_swiglu(xn, layer.w_up, layer.b_up)
+                   if sel is None and xn.shape[0] >= 256 and xn.shape[0] % 256 == 0
+                   else ops.swiglu(self._lin(xn, layer.w_up, layer.b_up, li, "w_up", sel)))
+            out = self._lin(act, layer.w_down, None, li, "w_down", sel)
         else:
-            out = ops.decode_linear(ops.gelu(ops.decode_linear(xn, layer.w_up, layer.b_up)), layer.w_down)
+            out = self._lin(ops.gelu(self._lin(xn, layer.w_up, layer.b_up, li, "w_up", sel)), layer.w_down, None, li,
+                            "w_down", sel)
         out = self._reduce(out)  # row-parallel down projection
         if layer.b_down is not None:
             out = out + layer.b_down
@@ -345,7 +391,9 @@ class InferenceEngine:
         # own rows, so attention can run as packed-document flash attention (doc_start per token)
         fresh = bool(chunks) and all(c.start == 0 for c in chunks)
         doc = np.repeat(np.asarray(cu[:-1], dtype=np.int32), np.diff(cu)) if fresh else None
-        return {"op": "prefill", "ids": np.asarray(ids, dtype=np.int64), "pos": np.asarray(pos, dtype=np.int32),
+        lora = [c.seq.lora_slot for c in chunks]
+        extra = {"lora": lora} if any(s >= 0 for s in lora) else {}  # adapter slot per chunk
+        return {**extra, "op": "prefill", "ids": np.asarray(ids, dtype=np.int64), "pos": np.asarray(pos, dtype=np.int32),
                 "slots": np.concatenate(slots) if slots else np.zeros(0, dtype=np.int64), "cu": cu, "ctx": ctx,
                 "bt": bt, "last": last, "work": ops.prefill_work_list(cu), "doc": doc}
 
@@ -379,7 +427,11 @@ class InferenceEngine:
         # (one prompt: plain causal attention, which also lets the kernel split the K/V range of
         # its few q-blocks over two workgroups — the split is off for packed documents)
         x = self._embed(ids, pos.long())
-        if self._norm_fold_ok(T):
+        # chunks of adapter sequences: contiguous row ranges, their deltas added per segment
+        sel = None
+        if plan.get("lora") is not None:
+            sel = [(plan["cu"][i], plan["cu"][i + 1], s) for i, s in enumerate(plan["lora"]) if s >= 0]
+        if self._norm_fold_ok(T, sel):
             h = self._prefill_layers_folded(x, pos, slots, fa, doc, bt, cu, ctx, work)
             self.stats["prefill_tokens"] += T
             if not plan["last"]:
@@ -391,18 +443,18 @@ class InferenceEngine:
         kc, vc = self.kv_cache.k, self.kv_cache.v
         for li, layer in enumerate(self.model.layers):
             xn, res = self._norm(layer, x, res, "attn")
-            q, k, v = self._qkv(layer, xn, pos, self.max_model_len, kc[li], vc[li], slots)
+            q, k, v = self._qkv(layer, xn, pos, self.max_model_len, kc[li], vc[li], slots, li, sel)
             if fa:
                 o = ops.flash_attention(q.view(1, T, layer.nq, layer.D), k.view(1, T, layer.nkv, layer.D),
                                         v.view(1, T, layer.nkv, layer.D), causal=True, doc_start=doc)
             else:
                 o = ops.paged_prefill_attention(q.view(T, layer.nq, layer.D), kc[li], vc[li], bt, cu, ctx,
                                                 work=work)
-            a = self._reduce(ops.decode_linear(o.view(T, -1), layer.wo))
+            a = self._reduce(self._lin(o.view(T, -1), layer.wo, None, li, "wo", sel))
             if layer.bo is not None:
                 a = a + layer.bo
             xn, res = self._norm(layer, a, res, "mlp")
-            x = self._mlp(layer, xn)
+            x = self._mlp(layer, xn, li, sel)
         self.stats["prefill_tokens"] += T
         if not plan["last"]:
             return torch.empty(0, self.cfg.vocab_size, device=d, dtype=x.dtype)
@@ -446,9 +498,13 @@ class InferenceEngine:
         x = self._embed(ids, pos.long())
         res = None
         kc, vc = self.kv_cache.k, self.kv_cache.v
+        sel = None  # adapter segments: the chunks' row ranges, then one row per decode sequence
+        if pp.get("lora") is not None or dp.get("lora") is not None:
+            sel = [(pp["cu"][i], pp["cu"][i + 1], s) for i, s in enumerate(pp.get("lora") or []) if s >= 0]
+            sel += [(Tp + i, Tp + i + 1, s) for i, s in enumerate(dp.get("lora") or []) if s >= 0]
         for li, layer in enumerate(self.model.layers):
             xn, res = self._norm(layer, x, res, "attn")
-            q, k, v = self._qkv(layer, xn, pos, self.max_model_len, kc[li], vc[li], slots)
+            q, k, v = self._qkv(layer, xn, pos, self.max_model_len, kc[li], vc[li], slots, li, sel)
             if fa:
                 op = ops.flash_attention(q[:Tp].reshape(1, Tp, layer.nq, layer.D),
                                          k[:Tp].reshape(1, Tp, layer.nkv, layer.D),
@@ -459,11 +515,11 @@ class InferenceEngine:
             od = ops.paged_attention_decode(q[Tp:].reshape(Td, layer.nq, layer.D).contiguous(), kc[li], vc[li], bt_d,
                                             ctx_d)
             o = torch.cat([op.reshape(Tp, -1), od.reshape(Td, -1)])
-            a = self._reduce(ops.decode_linear(o, layer.wo))
+            a = self._reduce(self._lin(o, layer.wo, None, li, "wo", sel))
             if layer.bo is not None:
                 a = a + layer.bo
             xn, res = self._norm(layer, a, res, "mlp")
-            x = self._mlp(layer, xn)
+            x = self._mlp(layer, xn, li, sel)
         self.stats["prefill_tokens"] += Tp
         self.stats["decode_tokens"] += Td
         self.stats["mixed_steps"] = self.stats.get("mixed_steps", 0) + 1
@@ -491,21 +547,22 @@ class InferenceEngine:
                 and all(l.attn_norm_b is None and l.mlp_norm_b is None for l in m.layers)
                 and self.knobs.decode_fused)
 
-    def _decode_body(self, ids, positions, slots, block_tables, ctx_lens) -> torch.Tensor:
+    def _decode_body(self, ids, positions, slots, block_tables, ctx_lens, lora_idx=None) -> torch.Tensor:
+        """``lora_idx``: int32 [rows], the adapter slot of every row (-1 = none), or None."""
         if self._fused_decode(ids.shape[0]):
-            return self._decode_body_fused(ids, positions, slots, block_tables, ctx_lens)
+            return self._decode_body_fused(ids, positions, slots, block_tables, ctx_lens, lora_idx)
         x = self._embed(ids, positions)
         res = None
         kc, vc = self.kv_cache.k, self.kv_cache.v
         for li, layer in enumerate(self.model.layers):
             xn, res = self._norm(layer, x, res, "attn")
-            q, k, v = self._qkv(layer, xn, positions, self.max_model_len, kc[li], vc[li], slots)
+            q, k, v = self._qkv(layer, xn, positions, self.max_model_len, kc[li], vc[li], slots, li, lora_idx)
             o = ops.paged_attention_decode(q, kc[li], vc[li], block_tables, ctx_lens)
-            a = self._reduce(ops.decode_linear(o.view(o.shape[0], -1), layer.wo))
+            a = self._reduce(self._lin(o.view(o.shape[0], -1), layer.wo, None, li, "wo", lora_idx))
             if layer.bo is not None:
                 a = a + layer.bo
             xn, res = self._norm(layer, a, res, "mlp")
-            x = self._mlp(layer, xn)
+            x = self._mlp(layer, xn, li, lora_idx)
         return self._final(x, res)
 
     _W8_NAMES = ("wqkv", "wo", "w_up", "w_down")
@@ -566,7 +623,7 @@ class InferenceEngine:
                 return q
         return getattr(layer, name), None
 
-    def _decode_body_fused(self, ids, positions, slots, block_tables, ctx_lens) -> torch.Tensor:
+    def _decode_body_fused(self, ids, positions, slots, block_tables, ctx_lens, lora_idx=None) -> torch.Tensor:
         m = self.model
         eps = self.cfg.layer_norm_eps
         layers = m.layers
@@ -579,19 +636,22 @@ class InferenceEngine:
                 return ops.decode_linear(x, w)
             return ops.decode_linear_int4(x, w, s) if w.dtype == torch.uint8 else ops.decode_linear_fp8(x, w, s)
 
+        def rows(li, name):  # the projection's adapters under this step's row selection
+            return None if lora_idx is None else ops.LoRARows(lora_idx, *self._lora[li][name])
+
         n = ids.shape[0]
         for li, layer in enumerate(layers):
             (wqkv, sqkv), (wo, so) = self._dw(li, layer, "wqkv", n), self._dw(li, layer, "wo", n)
             (wu, su), (wd, sd) = self._dw(li, layer, "w_up", n), self._dw(li, layer, "w_down", n)
             o = ops.decode_attention_qkv(xn, wqkv, layer.bqkv, self.rope[0], self.rope[1], layer.nq,
                                          layer.nkv, positions, kc[li], vc[li], slots, block_tables, ctx_lens,
-                                         w_scale=sqkv)
+                                         w_scale=sqkv, lora=rows(li, "wqkv"))
             if tp:  # row-parallel o-proj partial -> one kernel: all-reduce + bias + residual + RMSNorm
                 xn, res = self._reduce_add_rmsnorm(lin(o.view(o.shape[0], -1), wo, so), layer.bo,
                                                    res, layer.mlp_norm_w, eps)
             else:
                 xn, res = ops.decode_linear_add_rmsnorm(o.view(o.shape[0], -1), wo, layer.bo, res,
-                                                        layer.mlp_norm_w, eps, w_scale=so)
+                                                        layer.mlp_norm_w, eps, w_scale=so, lora=rows(li, "wo"))
             nw = layers[li + 1].attn_norm_w if li + 1 < len(layers) else m.final_norm_w
             if layer.moe is not None:  # routed experts: all routing stays on the device
                 up_t, down_t = self._moe[li]
@@ -599,11 +659,12 @@ class InferenceEngine:
                 act = ops.moe_decode_up_swiglu(xn, up_t, topi)
                 xn, res = ops.moe_decode_down_add_rmsnorm(act, down_t, topi, topw, res, nw, eps)
                 continue
-            act = ops.decode_up_swiglu(xn, wu, layer.b_up, w_scale=su)  # the local F shard
+            act = ops.decode_up_swiglu(xn, wu, layer.b_up, w_scale=su, lora=rows(li, "w_up"))  # the local F shard
             if tp:
                 xn, res = self._reduce_add_rmsnorm(lin(act, wd, sd), layer.b_down, res, nw, eps)
             else:
-                xn, res = ops.decode_linear_add_rmsnorm(act, wd, layer.b_down, res, nw, eps, w_scale=sd)
+                xn, res = ops.decode_linear_add_rmsnorm(act, wd, layer.b_down, res, nw, eps, w_scale=sd,
+                                                        lora=rows(li, "w_down"))
         if self._wq_head is not None and n <= self.W8_MAX_ROWS:
             return self._gather_vocab(lin(xn, *self._wq_head))
         return self._gather_vocab(ops.decode_linear(xn, m.head_weight()))
@@ -635,7 +696,7 @@ class InferenceEngine:
                         "top_lp": torch.zeros(nb, W, dtype=torch.float32).pin_memory()}
         bufs["host_lp"] = [host(), host()]
 
-    def _static(self, nb: int) -> Dict:
+    def _static(self, nb: int, lora: bool = False) -> Dict:
         d = self.device
         bufs = {"ids": torch.zeros(nb, dtype=torch.long, device=d),
                 "positions": torch.zeros(nb, dtype=torch.int32, device=d),
@@ -647,6 +708,10 @@ class InferenceEngine:
                 "temp": torch.zeros(nb, dtype=torch.float32, device=d),
                 "topk": torch.zeros(nb, dtype=torch.int32, device=d),
                 "topp": torch.ones(nb, dtype=torch.float32, device=d)}
+        bufs["staged"] = self._STAGED
+        if lora:  # the adapter slot of every row, staged with the step's other inputs
+            bufs["lora_idx"] = torch.full((nb,), -1, dtype=torch.int32, device=d)
+            bufs["staged"] = self._STAGED + ("lora_idx",)
         # pinned host staging of the step inputs, two sets: an asynchronous step refills one while
         # the other's H2D copies may still be queued behind the step in flight (a non_blocking
         # copy from pageable memory would be synchronous)
@@ -655,7 +720,7 @@ class InferenceEngine:
         for _ in range(2):
             # initialised from the device defaults: rows past the live batch are copied too and
             # must stay valid (block id 0, context 1) for the padded graph rows
-            h = {k: bufs[k].to("cpu") for k in self._STAGED}
+            h = {k: bufs[k].to("cpu") for k in bufs["staged"]}
             stage.append({k: (v.pin_memory() if pin else v) for k, v in h.items()})
         bufs["stage"] = stage
         bufs["flip"] = 0
@@ -669,7 +734,7 @@ class InferenceEngine:
         """Decode step + sampling; the sampled ids also become the next step's input ids (the
         asynchronous path launches step N + 1 without reading step N's tokens first)."""
         bufs["logits"] = self._decode_body(bufs["ids"], bufs["positions"], bufs["slots"], bufs["block_tables"],
-                                           bufs["ctx_lens"])
+                                           bufs["ctx_lens"], bufs.get("lora_idx"))
         if "slot" in bufs:  # the extended graph: penalties, logprobs and the state update ride in the sampler
             counts, mask = self._sampler_state
             bufs["toks"], bufs["lp"], bufs["top_ids"], bufs["top_lp"] = ops.sample_ext(
@@ -679,8 +744,15 @@ class InferenceEngine:
             bufs["toks"] = ops.sample(bufs["logits"].contiguous(), bufs["temp"], bufs["topk"], bufs["topp"], bufs["u"])
         bufs["ids"].copy_(bufs["toks"])
 
-    def _capture(self, nb: int, ext: bool = False):
-        bufs = self._static(nb)
+    def _graph_family(self, nb: int, ext: bool, lora: bool):
+        """(dict, key) of the graph an ``nb``-row step replays: plain, extended sampler, or -- a step
+        with an adapter row -- the LoRA family, keyed (bucket, extended)."""
+        if lora:
+            return self._graphs_lora, (nb, ext)
+        return (self._graphs_ext if ext else self._graphs), nb
+
+    def _capture(self, nb: int, ext: bool = False, lora: bool = False):
+        bufs = self._static(nb, lora)
         if ext:
             self._static_ext(nb, bufs)
         s = torch.cuda.Stream(device=self.device)
@@ -692,14 +764,15 @@ class InferenceEngine:
         g = torch.cuda.CUDAGraph()
         with graph_capture_gc_guard(), torch.cuda.graph(g):
             self._graph_body(bufs)
-        (self._graphs_ext if ext else self._graphs)[nb] = (g, bufs)
+        graphs, key = self._graph_family(nb, ext, lora)
+        graphs[key] = (g, bufs)
 
     def release_graphs(self) -> None:
         """Drop the captured decode graphs (they hold the RCCL communicator's captured
         collectives: release them before ``destroy_process_group``)."""
-        if (self._graphs or self._graphs_ext) and self.device.type == "cuda":
+        if (self._graphs or self._graphs_ext or self._graphs_lora) and self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
-        for graphs in (self._graphs, self._graphs_ext):
+        for graphs in (self._graphs, self._graphs_ext, self._graphs_lora):
             for g, _ in graphs.values():
                 g.reset()
             graphs.clear()
@@ -725,6 +798,8 @@ class InferenceEngine:
         self._sampler_free = []
         self.kv_cache = None
         self._wq = self._wq_head = None
+        self._lora = None
+        self._lora_slots, self._lora_salt, self._lora_scale = {}, {}, {}
         self._nf = None
         self._moe = None
         self.rope = None
@@ -737,8 +812,14 @@ class InferenceEngine:
     def __exit__(self, *exc) -> None:
         self.close()
 
+    @staticmethod
+    def _lora_rows(seqs: List[Sequence]) -> Dict:
+        """``{"lora": [slot per row]}`` for a decode plan when a row has an adapter, else nothing."""
+        rows = [s.lora_slot for s in seqs]
+        return {"lora": rows} if any(r >= 0 for r in rows) else {}
+
     def decode_plan(self, seqs: List[Sequence]) -> Dict:
-        return {"op": "decode", "ids": [s.last_id for s in seqs], "positions": [s.num_tokens - 1 for s in seqs],
+        return {**self._lora_rows(seqs), "op": "decode", "ids": [s.last_id for s in seqs], "positions": [s.num_tokens - 1 for s in seqs],
                 "slots": [s._decode_slot for s in seqs], "ctx": [self.kv.num_tokens(s.seq_id) for s in seqs],
                 "bt": np.asarray(self.kv.block_tables([s.seq_id for s in seqs], self.max_blocks_per_seq))}
 
@@ -756,9 +837,10 @@ class InferenceEngine:
             g, b = self._stage_and_replay(plan, cont=False)
             return b["logits"][:n]
         d = self.device
+        lora = torch.tensor(plan["lora"], dtype=torch.int32, device=d) if plan.get("lora") is not None else None
         return self._decode_body(torch.tensor(ids, device=d), torch.tensor(positions, dtype=torch.int32, device=d),
                                  torch.tensor(slots, device=d), torch.from_numpy(bt).to(d),
-                                 torch.tensor(ctx, dtype=torch.int32, device=d))
+                                 torch.tensor(ctx, dtype=torch.int32, device=d), lora)
 
     def _stage_and_replay(self, plan: Dict, cont: bool):
         """Fill one host staging set with the step's inputs, copy them (asynchronously) into the
@@ -773,10 +855,11 @@ class InferenceEngine:
         # a step with extended rows (``_launch_decode`` set ``_ext_step``) replays the bucket's
         # extended graph; its per-row penalty parameters follow the ``params_key`` rule below
         ext = self._ext_step if "temp" in plan else None
-        graphs = self._graphs_ext if ext is not None else self._graphs
-        if nb not in graphs:
-            self._capture(nb, ext is not None)
-        g, b = graphs[nb]
+        lora = plan.get("lora")  # a step with an adapter row replays the bucket's LoRA graph
+        graphs, gkey = self._graph_family(nb, ext is not None, lora is not None)
+        if gkey not in graphs:
+            self._capture(nb, ext is not None, lora is not None)
+        g, b = graphs[gkey]
         h = b["stage"][b["flip"]]
         b["flip"] ^= 1
         hn = {k: v.numpy() for k, v in h.items()}
@@ -789,6 +872,9 @@ class InferenceEngine:
         hn["ctx_lens"][:] = 1
         hn["ctx_lens"][:n] = plan["ctx"]
         hn["u"][:n] = plan["u"] if "u" in plan else 0.0
+        if lora is not None:
+            hn["lora_idx"][:] = -1
+            hn["lora_idx"][:n] = lora
         if "temp" in plan:
             key = (np.asarray(plan["temp"], dtype=np.float32).tobytes(), np.asarray(plan["topk"], dtype=np.int32).tobytes(),
                    np.asarray(plan["topp"], dtype=np.float32).tobytes())
@@ -811,7 +897,7 @@ class InferenceEngine:
                 b["topk"][:n].copy_(torch.from_numpy(np.frombuffer(key[1], dtype=np.int32).copy()).to(d))
                 b["topp"][:n].copy_(torch.from_numpy(np.frombuffer(key[2], dtype=np.float32).copy()).to(d))
                 b["params_key"] = key
-        for k in self._STAGED:
+        for k in b["staged"]:
             if cont and k == "ids":
                 continue
             b[k].copy_(h[k], non_blocking=True)
@@ -860,7 +946,8 @@ class InferenceEngine:
         d = self.device
         host_lp = None
         if self._graph_ok(n):
-            b = (self._graphs_ext if ext is not None else self._graphs)[self._bucket(n)][1]
+            graphs, gkey = self._graph_family(self._bucket(n), ext is not None, plan.get("lora") is not None)
+            b = graphs[gkey][1]
             out = b["host_toks"][b["tflip"]]
             if want_lp:  # the logprobs ride the same pinned D2H copy as the tokens
                 host_lp = b["host_lp"][b["tflip"]]
@@ -895,7 +982,9 @@ class InferenceEngine:
         logits = self._decode_body(ids, torch.as_tensor(np.asarray(plan["positions"], dtype=np.int32)).to(d),
                                    torch.as_tensor(np.asarray(plan["slots"], dtype=np.int64)).to(d),
                                    torch.from_numpy(np.asarray(plan["bt"])).to(d),
-                                   torch.as_tensor(np.asarray(plan["ctx"], dtype=np.int32)).to(d))
+                                   torch.as_tensor(np.asarray(plan["ctx"], dtype=np.int32)).to(d),
+                                   torch.as_tensor(np.asarray(plan["lora"], dtype=np.int32)).to(d)
+                                   if plan.get("lora") is not None else None)
         temp = torch.from_numpy(np.asarray(plan["temp"], dtype=np.float32)).to(d)
         topk = torch.from_numpy(np.asarray(plan["topk"], dtype=np.int32)).to(d)
         topp = torch.from_numpy(np.asarray(plan["topp"], dtype=np.float32)).to(d)
@@ -950,7 +1039,8 @@ class InferenceEngine:
                 raise RuntimeError("KV append failed despite free blocks")
             s._decode_slot = slot
             s.kv_len += 1
-        plan = {"positions": [s.num_tokens for s in seqs], "slots": [s._decode_slot for s in seqs],
+        plan = {**self._lora_rows(seqs),
+                "positions": [s.num_tokens for s in seqs], "slots": [s._decode_slot for s in seqs],
                 "ctx": [self.kv.num_tokens(s.seq_id) for s in seqs],
                 "bt": np.asarray(self.kv.block_tables([s.seq_id for s in seqs], self.max_blocks_per_seq))}
         self.stats["async_continued"] = self.stats.get("async_continued", 0) + 1
@@ -1056,8 +1146,121 @@ class InferenceEngine:
                     on_finish=None) -> Sequence:
         seq = Sequence(prompt_ids=list(prompt_ids), params=params, request_id=request_id, on_token=on_token,
                        on_finish=on_finish)
+        name = getattr(params, "lora", None)
+        if name is not None:
+            if name not in self._lora_slots:
+                raise ValueError(f"unknown LoRA adapter {name!r} (loaded: {sorted(self._lora_slots) or 'none'})")
+            seq.lora_slot, seq.lora_salt = self._lora_slots[name], self._lora_salt[name]
         self.scheduler.add(seq)
         return seq
+
+    # ------------------------------------------------------------------ LoRA adapters
+    def _lora_projections(self, layer) -> Dict[str, torch.Tensor]:
+        from .lora import PROJECTIONS
+
+        return {n: getattr(layer, n) for n in PROJECTIONS
+                if isinstance(getattr(layer, n, None), torch.Tensor) and getattr(layer, n).dim() == 2}
+
+    def _alloc_lora(self):
+        """Per layer and projection the resident stacked adapters ``(A_all [slots, R, K], B_all
+        [slots, N, R], scale_all [slots] fp32)``, all zeros: loading an adapter is a ``copy_`` into
+        its slot, the addresses never change, so captured graphs stay valid across loads."""
+        from .lora import LORA_RANKS
+
+        S, R = self.max_loras, self.max_lora_rank
+        if R not in LORA_RANKS:
+            raise ValueError(f"max_lora_rank must be one of {LORA_RANKS}, got {R}")
+        out, nbytes = [], 0
+        for li, layer in enumerate(self.model.layers):
+            d = {}
+            for name, w in self._lora_projections(layer).items():
+                N, K = w.shape
+                if self.device.type == "cuda" and (N % 64 or K % 64):
+                    raise ValueError(f"LoRA: layer {li} {name} [{N}, {K}] does not fit the adapter kernels "
+                                     "(out and in features multiples of 64)")
+                d[name] = (torch.zeros(S, R, K, dtype=self.dtype, device=self.device),
+                           torch.zeros(S, N, R, dtype=self.dtype, device=self.device),
+                           torch.zeros(S, dtype=torch.float32, device=self.device))
+                nbytes += sum(t.numel() * t.element_size() for t in d[name])
+            out.append(d)
+        log.info("engine: LoRA adapter slots: %d x rank %d on %d projections: %.3f GB (out of the KV cache budget)",
+                 S, R, sum(len(d) for d in out), nbytes / 1e9)
+        return out
+
+    def _lora_refusal(self) -> Optional[str]:
+        if self.cfg.is_moe:
+            return "LoRA adapters not supported with MoE models (routed-expert adapters are out of scope)"
+        if self.tp > 1:
+            return f"LoRA adapters not supported with tensor parallelism > 1 (TP = {self.tp})"
+        return None
+
+    @torch.no_grad()
+    def load_lora(self, name: str, adapter) -> int:
+        """Make ``adapter`` (a ``LoRAAdapter``, or the path of an adapter directory) selectable as
+        ``SamplingParams(lora=name)``; returns its slot.  Ranks below ``max_lora_rank`` are
+        zero-padded, larger ones refused.  Every load draws a fresh prefix-cache salt: K/V blocks
+        computed under an earlier adapter of the same name are never re-attached."""
+        import os
+
+        from .lora import LoRAAdapter
+
+        why = self._lora_refusal()
+        if why is not None:
+            raise ValueError(why)
+        if self._lora is None:
+            raise ValueError("this engine has no LoRA slots (max_loras = 0)")
+        if name in self._lora_slots:
+            raise ValueError(f"LoRA adapter {name!r} is already loaded (unload_lora first)")
+        if len(self._lora_slots) >= self.max_loras:
+            raise ValueError(f"cannot load LoRA adapter {name!r}: max_loras = {self.max_loras} adapters are loaded")
+        if not isinstance(adapter, LoRAAdapter):
+            adapter = LoRAAdapter.load(str(adapter), self.cfg)
+        R = self.max_lora_rank
+        staged = []  # everything validated and padded before a slot is touched
+        known = set()
+        for li, d in enumerate(self._lora):
+            for pname, (A_all, B_all, _) in d.items():
+                known.add((li, pname))
+                staged.append((li, pname, adapter.padded(li, pname, R, B_all.shape[1], A_all.shape[2])))
+        stray = sorted(set(adapter.tensors) - known)
+        if stray:
+            raise ValueError(f"LoRA adapter {name!r} targets projections the model does not have: {stray[:4]}")
+        slot = min(set(range(self.max_loras)) - set(self._lora_slots.values()))
+        for li, pname, ab in staged:
+            A_all, B_all, sc = self._lora[li][pname]
+            if ab is None:  # a missing (layer, projection) means a zero delta
+                A_all[slot].zero_()
+                B_all[slot].zero_()
+            else:
+                A_all[slot].copy_(ab[0].to(A_all.dtype))
+                B_all[slot].copy_(ab[1].to(B_all.dtype))
+            sc[slot] = adapter.scale
+        self._lora_slots[name] = slot
+        self._lora_salt[name] = os.urandom(16)
+        self._lora_scale[slot] = adapter.scale
+        return slot
+
+    @torch.no_grad()
+    def unload_lora(self, name: str) -> None:
+        """Free ``name``'s slot (zeroed).  Raises while a live sequence uses the adapter."""
+        if name not in self._lora_slots:
+            raise ValueError(f"unknown LoRA adapter {name!r}")
+        slot = self._lora_slots[name]
+        live = [s for s in list(self.scheduler.running) + list(self.scheduler.waiting)
+                if s.lora_slot == slot and s.status != "finished"]
+        if live:
+            raise RuntimeError(f"LoRA adapter {name!r} is in use by {len(live)} live sequence(s)")
+        for d in self._lora:
+            for A_all, B_all, sc in d.values():
+                A_all[slot].zero_()
+                B_all[slot].zero_()
+                sc[slot] = 0.0
+        del self._lora_slots[name], self._lora_salt[name]
+        self._lora_scale.pop(slot, None)
+
+    @property
+    def loras(self) -> List[str]:
+        return sorted(self._lora_slots)
 
     def _append(self, seq: Sequence, tok: int, lp=None) -> None:
         """``lp``: the token's row of :meth:`_lp_rows` (a sequence with ``logprobs`` set)."""

@@ -45,20 +45,22 @@ class PrefixCache:
     def __len__(self) -> int:
         return len(self._blocks)
 
-    def _hashes(self, ids: Sequence[int], nblocks: int) -> List[bytes]:
-        out, h = [], b""
+    def _hashes(self, ids: Sequence[int], nblocks: int, salt: bytes = b"") -> List[bytes]:
+        out, h = [], salt
         for i in range(nblocks):
             h = _block_hash(h, ids[i * self.bs:(i + 1) * self.bs])
             out.append(h)
         return out
 
-    def match(self, ids: Sequence[int]) -> List[int]:
+    def match(self, ids: Sequence[int], salt: bytes = b"") -> List[int]:
         """Block ids of the longest cached prefix of ``ids`` in whole blocks, leaving at least one
-        token of ``ids`` uncached (its logits are what the prefill must produce)."""
+        token of ``ids`` uncached (its logits are what the prefill must produce).  ``salt`` seeds the
+        hash chain: blocks match only under the salt they were inserted with (K/V computed under a
+        LoRA adapter; without a salt the hashes are the unsalted ones)."""
         self.stats["lookups"] += 1
         nfull = (len(ids) - 1) // self.bs
         blocks: List[int] = []
-        for h in self._hashes(ids, nfull):
+        for h in self._hashes(ids, nfull, salt):
             b = self._blocks.get(h)
             if b is None:
                 break
@@ -68,7 +70,7 @@ class PrefixCache:
         return blocks
 
     def insert(self, ids: Sequence[int], table: Sequence[int], num_computed: int,
-               hashes: Optional[List[bytes]] = None, start: int = 0) -> None:
+               hashes: Optional[List[bytes]] = None, start: int = 0, salt: bytes = b"") -> None:
         """Index every fully computed block of a sequence (``ids`` its tokens, ``table`` its block
         table, ``num_computed`` the positions whose K/V are in the cache).  ``hashes``: the
         sequence's chain-hash list, extended in place (only new blocks are hashed); ``start``:
@@ -76,7 +78,7 @@ class PrefixCache:
         nfull = min(num_computed // self.bs, len(table))
         if hashes is None:
             hashes = []
-        h = hashes[-1] if hashes else b""
+        h = hashes[-1] if hashes else salt
         for i in range(len(hashes), nfull):
             h = _block_hash(h, ids[i * self.bs:(i + 1) * self.bs])
             hashes.append(h)

@@ -50,6 +50,7 @@ class SamplingParams:
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     logprobs: Optional[int] = None
+    lora: Optional[str] = None  # name of a loaded LoRA adapter (``InferenceEngine.load_lora``)
 
     @property
     def penalized(self) -> bool:
@@ -92,6 +93,8 @@ class Sequence:
     block_hashes: List[bytes] = field(default_factory=list, repr=False)
     indexed_blocks: int = 0
     sampler_slot: int = -1  # row of the engine's sampler state (penalties), -1 = none held
+    lora_slot: int = -1  # the engine's slot of ``params.lora``, resolved at add_request; -1 = base model
+    lora_salt: bytes = field(default=b"", repr=False)  # seeds the prefix-cache hash chain (K/V depend on the adapter)
 
     @property
     def all_ids(self) -> List[int]:
@@ -187,7 +190,7 @@ class ContinuousBatchScheduler:
         The matched prefix blocks are held only by the cache until ``add_sequence_shared``
         takes its references, so the reservation must not evict them."""
         n = seq.num_tokens  # a resumed sequence also re-covers its generated tokens
-        prefix = self.prefix_cache.match(seq.all_ids) if self.prefix_cache is not None else []
+        prefix = self.prefix_cache.match(seq.all_ids, salt=seq.lora_salt) if self.prefix_cache is not None else []
         need = self.kv.blocks_needed(n + self.kv_block_size()) - len(prefix)
         if not self._reserve(need, protect=prefix):
             return False
@@ -261,7 +264,7 @@ class ContinuousBatchScheduler:
         if (self.prefix_cache is not None and seq.status == "running"
                 and seq.num_computed // self.block_size > seq.indexed_blocks):
             self.prefix_cache.insert(seq.all_ids, self.kv.block_table(seq.seq_id), seq.num_computed,
-                                     hashes=seq.block_hashes, start=seq.indexed_blocks)
+                                     hashes=seq.block_hashes, start=seq.indexed_blocks, salt=seq.lora_salt)
             seq.indexed_blocks = seq.num_computed // self.block_size
 
     def kv_block_size(self) -> int:
@@ -293,7 +296,8 @@ class ContinuousBatchScheduler:
             except (KeyError, IndexError, RuntimeError):
                 table = []
             if table:
-                self.prefix_cache.insert(seq.all_ids, table, seq.num_computed, hashes=seq.block_hashes)
+                self.prefix_cache.insert(seq.all_ids, table, seq.num_computed, hashes=seq.block_hashes,
+                                         salt=seq.lora_salt)
         self.kv.free_sequence(seq.seq_id)
         if self.on_release is not None:
             self.on_release(seq)

@@ -46,6 +46,9 @@ class GenerationRequest(BaseModel):
     frequency_penalty: float = 0.0
     repetition_penalty: float = 1.0
     logprobs: Optional[int] = None
+    # name of a loaded LoRA adapter (``InferenceEngine.load_lora``); a ``model`` value that equals a
+    # loaded adapter's name selects it too, any other ``model`` value is served by the base
+    lora: Optional[str] = None
 
 
 def validate_request(req: GenerationRequest) -> None:
@@ -76,7 +79,8 @@ class InferenceServer:
     def __init__(self, model_path: str, host: str = "0.0.0.0", port: int = 8080, max_batch_size: int = 8,
                  max_batch_tokens: int = 8192, max_concurrent: int = 128, scheduler: str = "dynamic",
                  device: str = "auto", kv_cache_fraction: float = 0.85, block_size: int = 16, use_graphs: bool = True,
-                 tensor_parallel: int = 1, engine=None, kv_cache_dtype: str = "auto", weight_dtype: str = "auto"):
+                 tensor_parallel: int = 1, engine=None, kv_cache_dtype: str = "auto", weight_dtype: str = "auto",
+                 loras: Optional[Dict[str, str]] = None, max_loras: int = 0, max_lora_rank: int = 16):
         from fastapi import FastAPI, HTTPException
         from fastapi.middleware.cors import CORSMiddleware
         from fastapi.responses import PlainTextResponse, StreamingResponse
@@ -86,7 +90,9 @@ class InferenceServer:
         self.engine_kwargs = dict(model_path=model_path, device=device, max_batch_size=max_batch_size,
                                   max_batch_tokens=max_batch_tokens, kv_cache_fraction=kv_cache_fraction,
                                   block_size=block_size, scheduler=scheduler, use_graphs=use_graphs,
-                                  kv_cache_dtype=kv_cache_dtype, weight_dtype=weight_dtype)
+                                  kv_cache_dtype=kv_cache_dtype, weight_dtype=weight_dtype,
+                                  max_loras=max(max_loras, len(loras or {})), max_lora_rank=max_lora_rank)
+        self.loras = dict(loras or {})  # adapter name -> directory, loaded when the engine starts
         if tensor_parallel != 1 and engine is None:
             raise ValueError("TP serving runs one engine per rank under torchrun: use llmctl.serve.tp "
                              "(`llmctl serve start --tensor-parallel N` launches it)")
@@ -127,6 +133,7 @@ class InferenceServer:
                 raise HTTPException(status_code=503, detail="Server at capacity")
             try:
                 validate_request(req)
+                self._lora_name(req)  # an unknown adapter is refused before a stream starts
             except ValueError as e:
                 raise HTTPException(status_code=400, detail=str(e))
             if req.stream:
@@ -138,8 +145,12 @@ class InferenceServer:
 
         @app.get("/v1/models")
         async def models():
-            return {"object": "list", "data": [{"id": self.model_name, "object": "model", "created": int(time.time()),
-                                                "owned_by": "llmctl"}]}
+            now = int(time.time())
+            data = [{"id": self.model_name, "object": "model", "created": now, "owned_by": "llmctl"}]
+            for name in (self.engine.loras if self.engine is not None else []):  # adapters: children of the base
+                data.append({"id": name, "object": "model", "created": now, "owned_by": "llmctl",
+                             "parent": self.model_name})
+            return {"object": "list", "data": data}
 
         @app.get("/health")
         async def health():
@@ -167,6 +178,8 @@ class InferenceServer:
 
             self.engine = InferenceEngine(**self.engine_kwargs)
             self._own_engine = True  # closed by this server's shutdown (a passed-in engine is the caller's)
+            for name, path in self.loras.items():
+                self.engine.load_lora(name, path)
         if self._thread is None:
             self._stop = False
             self._thread = threading.Thread(target=self._engine_loop, name="llmctl-engine", daemon=True)
@@ -210,6 +223,16 @@ class InferenceServer:
                     return
 
     # ------------------------------------------------------------------ request handling
+    def _lora_name(self, req: GenerationRequest) -> Optional[str]:
+        """The adapter a request selects: its ``lora`` field (unknown: ``ValueError``), else a
+        ``model`` value that names a loaded adapter, else None (the base model)."""
+        loaded = self.engine.loras if self.engine is not None else []
+        if req.lora is not None:
+            if req.lora not in loaded:
+                raise ValueError(f"unknown LoRA adapter {req.lora!r} (loaded: {list(loaded) or 'none'})")
+            return req.lora
+        return req.model if req.model is not None and req.model in loaded else None
+
     def _make_params(self, req: GenerationRequest):
         from .scheduler import SamplingParams
 
@@ -217,7 +240,8 @@ class InferenceServer:
         return SamplingParams(max_tokens=max(1, req.max_tokens), temperature=req.temperature, top_p=req.top_p,
                               top_k=req.top_k, stop=stop, ignore_eos=req.ignore_eos,
                               repetition_penalty=req.repetition_penalty, presence_penalty=req.presence_penalty,
-                              frequency_penalty=req.frequency_penalty, logprobs=req.logprobs)
+                              frequency_penalty=req.frequency_penalty, logprobs=req.logprobs,
+                              lora=self._lora_name(req))
 
     def _logprobs_payload(self, seq) -> Dict[str, Any]:
         """``choices[0]["logprobs"]`` in the OpenAI completions shape: four lists, one entry per
