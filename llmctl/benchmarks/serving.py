@@ -23,8 +23,9 @@ def run_serving_benchmark(model: str = "gpt-7b", prompt_length: int = 2048, gen_
                           sampling: Optional[Dict[str, Any]] = None, num_loras: int = 0,
                           lora_rank: int = 16) -> Dict[str, Any]:
     """``sampling``: extra ``SamplingParams`` fields of every request (penalties, logprobs), to
-    time the extended sampler end to end; the warm-up uses them too, so its graphs are captured
-    before the timed run.  ``num_loras``: that many random LoRA adapters of rank ``lora_rank`` are
+    time the extended sampler end to end (or ``guided_regex``: the guided sampler; such requests
+    end with EOS); the warm-up uses them too, so its graphs are captured before the timed run.
+    ``num_loras``: that many random LoRA adapters of rank ``lora_rank`` are
     loaded and request ``i`` runs on adapter ``i % num_loras`` (warm-up included)."""
     import torch
 
@@ -48,19 +49,20 @@ def run_serving_benchmark(model: str = "gpt-7b", prompt_length: int = 2048, gen_
     V = eng.cfg.vocab_size
     rng = random.Random(seed)
     extra = {k: v for k, v in (sampling or {}).items() if v is not None}
-    params = SamplingParams(max_tokens=gen_length, temperature=0.0, ignore_eos=True, **extra)
-    req_params = [params if not names else SamplingParams(max_tokens=gen_length, temperature=0.0, ignore_eos=True,
+    free = not any(k.startswith("guided_") for k in extra)  # a guided request ends with EOS, at its match's end
+    params = SamplingParams(max_tokens=gen_length, temperature=0.0, ignore_eos=free, **extra)
+    req_params = [params if not names else SamplingParams(max_tokens=gen_length, temperature=0.0, ignore_eos=free,
                                                           lora=names[i % len(names)], **extra)
                   for i in range(num_requests)]
     if warmup:  # capture decode graphs, warm the allocator and the GEMM / attention paths of the
         # full-length prefill batches the timed run will form (first-use costs stay out of TTFT)
         eng.generate([[1] * 16 for _ in range(min(max_batch_size, num_requests))],
-                     SamplingParams(max_tokens=4, temperature=0.0, ignore_eos=True, **extra))
+                     SamplingParams(max_tokens=4, temperature=0.0, ignore_eos=free, **extra))
         if names:  # the LoRA graph family of the warm-up's bucket
             eng.generate([[1] * 16 for _ in range(min(max_batch_size, num_requests))],
-                         SamplingParams(max_tokens=4, temperature=0.0, ignore_eos=True, lora=names[0], **extra))
+                         SamplingParams(max_tokens=4, temperature=0.0, ignore_eos=free, lora=names[0], **extra))
         eng.generate([[2] * prompt_length for _ in range(min(max_batch_size, num_requests))],
-                     SamplingParams(max_tokens=2, temperature=0.0, ignore_eos=True, **extra))
+                     SamplingParams(max_tokens=2, temperature=0.0, ignore_eos=free, **extra))
     prompts = [[rng.randrange(V) for _ in range(prompt_length)] for _ in range(num_requests)]
     arrivals = [0.0] * num_requests
     if qps:

@@ -58,6 +58,8 @@ def e2e(
     logprobs: Optional[int] = typer.Option(None, help="Top logprobs per token, 0..8 (extended sampler)"),
     num_loras: int = typer.Option(0, help="Random LoRA adapters to load; the requests are spread over them"),
     lora_rank: int = typer.Option(16, help="Rank of those adapters (16, 32 or 64)"),
+    guided_regex: Optional[str] = typer.Option(None, help="Guide every request by this regex (guided sampler; the "
+                                                          "requests then end with EOS when the match is complete)"),
 ) -> None:
     """End-to-end serving benchmark (TTFT p50/p99, TPOT, tokens/s).
 
@@ -72,7 +74,8 @@ def e2e(
                                 scheduler=scheduler, max_batch_tokens=max_batch_tokens, kv_cache_dtype=kv_cache_dtype,
                                 weight_dtype=weight_dtype, num_loras=num_loras, lora_rank=lora_rank,
                                 sampling={"presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty,
-                                          "repetition_penalty": repetition_penalty, "logprobs": logprobs})
+                                          "repetition_penalty": repetition_penalty, "logprobs": logprobs,
+                                          "guided_regex": guided_regex})
     console.print_json(json.dumps(res))
 
 

@@ -40,6 +40,8 @@ def start(
                                                                    "under NAME (repeatable)"),
     max_loras: int = typer.Option(0, help="Resident LoRA adapter slots (at least the number of --lora)"),
     max_lora_rank: int = typer.Option(16, help="Largest (fused) adapter rank: 16, 32 or 64"),
+    guide_table_words: int = typer.Option(1 << 18, help="Guided decoding: int32 words per guide table slot (a "
+                                                        "guide needs states x token classes of them)"),
 ) -> None:
     """Start the inference server."""
     from llmctl.serve.server import create_inference_server
@@ -85,7 +87,8 @@ def start(
                                      scheduler=scheduler, device=device, kv_cache_fraction=kv_cache_fraction,
                                      block_size=block_size, use_graphs=cuda_graphs, tensor_parallel=tensor_parallel,
                                      kv_cache_dtype=kv_cache_dtype, weight_dtype=weight_dtype, loras=loras,
-                                     max_loras=max_loras, max_lora_rank=max_lora_rank)
+                                     max_loras=max_loras, max_lora_rank=max_lora_rank,
+                                     guide_table_words=guide_table_words)
     try:
         server.run()
     except KeyboardInterrupt:
@@ -108,4 +111,5 @@ def main(
         raise typer.Exit(1)
     start(artifact=artifact, port=port, host=host, scheduler="dynamic", max_batch_size=8, max_batch_tokens=8192,
           max_concurrent=128, device=device, kv_cache_fraction=0.85, block_size=16, cuda_graphs=True,
-          tensor_parallel=1, kv_cache_dtype="auto", weight_dtype="auto", lora=None, max_loras=0, max_lora_rank=16)
+          tensor_parallel=1, kv_cache_dtype="auto", weight_dtype="auto", lora=None, max_loras=0, max_lora_rank=16,
+          guide_table_words=1 << 18)

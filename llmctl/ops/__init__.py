@@ -45,6 +45,8 @@ from .functional import (
     rope_qkv_cache,
     sample,
     sample_ext,
+    sample_guided,
+    guide_state_reset,
     sampler_state_reset,
     swiglu,
     transpose_,
@@ -57,7 +59,7 @@ __all__ = [
     "decode_linear_fp8", "decode_linear_int4", "decode_attention_qkv", "decode_fused_ok", "decode_linear_add_rmsnorm", "decode_qkv_rope_cache", "decode_up_swiglu",
     "flash_attention", "gelu", "kv_cache_write", "l2norm_sq", "layernorm", "paged_attention_decode",
     "paged_prefill_attention", "prefill_work_list", "attn_merge_",
-    "rmsnorm", "rope_qkv", "rope_flash_attention", "rope_qkv_cache", "sample", "sample_ext", "sampler_state_reset", "swiglu", "transpose_", "up_swiglu",
+    "rmsnorm", "rope_qkv", "rope_flash_attention", "rope_qkv_cache", "sample", "sample_ext", "sample_guided", "guide_state_reset", "sampler_state_reset", "swiglu", "transpose_", "up_swiglu",
     "rms_rstd", "linear_rowscale", "up_swiglu_rowscale", "linear_acc_",
     "LoRARows", "lora_delta", "MoEExpertTable", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",
 ]

@@ -6,6 +6,8 @@
 // mass of logits >= T are monotone in T), then an inverse-CDF draw over the kept tokens in
 // index order using a caller-provided uniform (so results are reproducible and the whole
 // step is hipGraph-capturable: no RNG state, no allocation, no host sync).
+#include <type_traits>
+
 #include "common.h"
 
 namespace llmctl {
@@ -29,7 +31,12 @@ __device__ __forceinline__ float bmax(float v, float* sm) {
   return r;
 }
 
-template <typename T>
+// kMasked (``sample_guided`` only): the row may hold -inf entries (tokens a guide does not allow).
+// They are never kept: the bisections start from the smallest *finite* entry (from -inf every
+// midpoint is -inf and top-k / top-p stop cutting), the inverse CDF skips them, and the rounding
+// fallback returns the last kept finite entry.  On a row without -inf both instantiations compute
+// the same values.
+template <typename T, bool kMasked = false>
 __global__ __launch_bounds__(256) void sample_kernel(const T* __restrict__ logits, const float* __restrict__ temp,
                                                       const int* __restrict__ topk, const float* __restrict__ topp,
                                                       const float* __restrict__ uni, int64_t* __restrict__ out, int V) {
@@ -106,7 +113,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const T* __restrict__ logit
   for (int i = tid; i < V; i += 256) {
     const float x = ld(lr, i) * inv_t;
     mx = fmaxf(mx, x);
-    mn = fminf(mn, x);
+    if (!kMasked || x > -INFINITY) mn = fminf(mn, x);
   }
   mx = bmax(mx, sm);
   mn = -bmax(-mn, sm);
@@ -150,7 +157,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const T* __restrict__ logit
   float cs = 0.f;
   for (int i = c0; i < c1; ++i) {
     const float x = ld(lr, i) * inv_t;
-    if (x >= thr) cs += __expf(x - mx);
+    if (x >= thr && (!kMasked || x > -INFINITY)) cs += __expf(x - mx);
   }
   scan[tid] = cs;
   if (tid == 0) found = -1;
@@ -170,7 +177,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const T* __restrict__ logit
   if (acc <= r && acc + cs > r) {
     for (int i = c0; i < c1; ++i) {
       const float x = ld(lr, i) * inv_t;
-      if (x >= thr) {
+      if (x >= thr && (!kMasked || x > -INFINITY)) {
         acc += __expf(x - mx);
         if (acc > r) {  // chunks are disjoint and ordered: exactly one thread gets here
           found = i;
@@ -183,11 +190,13 @@ __global__ __launch_bounds__(256) void sample_kernel(const T* __restrict__ logit
   if (tid == 0) {
     int f = found;
     if (f < 0) {  // r at the very top (rounding): last kept token
-      for (int i = V - 1; i >= 0; --i)
-        if (ld(lr, i) * inv_t >= thr) {
+      for (int i = V - 1; i >= 0; --i) {
+        const float x = ld(lr, i) * inv_t;
+        if (x >= thr && (!kMasked || x > -INFINITY)) {
           f = i;
           break;
         }
+      }
     }
     out[row] = f < 0 ? 0 : f;
   }
@@ -263,6 +272,112 @@ __global__ __launch_bounds__(256) void penalize_kernel(const T* __restrict__ log
   for (int i = V4 * 4 + threadIdx.x; i < V; i += 256) xr[i] = penalized(ld(lr, i), cr[i], mr[i], r, f, p);
 }
 
+// ---- sample_guided: sample_ext plus a token-class automaton per guided row.
+//
+// A guide (table slot g) is cls int32 [V] (class of every token), next int32 [S_g, C_g] (-1: not
+// allowed) and meta (S_g, C_g); a guided row owns one word of guide_state (index gslot): its
+// current automaton state.  The pre-pass writes -inf over the tokens the state does not allow,
+// the draw and the logprobs run on that row (kMasked / kGuided instantiations), and the logprob
+// kernel's thread 0 advances the state.  Launches of one stream order the state's read (pre-pass)
+// and its write (logprob kernel); rows of a launch never share a gslot.
+
+constexpr int kGuideMaxClasses = 8192;  // one state's row of ``next`` in 32 KB of static LDS
+
+struct GuideArgs {
+  const int* guide;  // [N] table slot, -1: unguided row
+  const int* gslot;  // [N] index into state
+  const int* cls;    // [G, V]
+  const int* next;   // [G, W], slot g holds next[s * C_g + c]
+  const int* meta;   // [G, 2] = (S_g, C_g)
+  int* state;        // [Sg]
+  int G, W, Sg;
+};
+
+// The row's guide, if it has a well-formed one: table slot, state word and the automaton state are
+// all range-checked here, so no later index can leave the arena.  Block-uniform.
+__device__ __forceinline__ bool guide_of(const GuideArgs& ga, long row, int& g, int& gs, int& st, int& C) {
+  g = ga.guide[row];
+  if (g < 0 || g >= ga.G) return false;
+  gs = ga.gslot[row];
+  if (gs < 0 || gs >= ga.Sg) return false;
+  const int S = ga.meta[2 * g];
+  C = ga.meta[2 * g + 1];
+  if (S < 1 || C < 1 || C > kGuideMaxClasses || (long)S * C > (long)ga.W) return false;
+  st = ga.state[gs];
+  return st >= 0 && st < S;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void penalize_mask_kernel(const T* __restrict__ logits, const int* __restrict__ slot,
+                                                             const float* __restrict__ rep,
+                                                             const float* __restrict__ freq,
+                                                             const float* __restrict__ pres,
+                                                             const int* __restrict__ counts,
+                                                             const unsigned char* __restrict__ pmask,
+                                                             float* __restrict__ out, int V, int S, GuideArgs ga) {
+  __shared__ int nx[kGuideMaxClasses];
+  const long row = blockIdx.x;
+  const T* lr = logits + row * (long)V;
+  float* xr = out + row * (long)V;
+  int g, gs, st, C = 0;
+  const bool guided = guide_of(ga, row, g, gs, st, C);
+  const int* cl = nullptr;
+  if (guided) {  // this state's row of next into LDS
+    const int* nr = ga.next + (long)g * ga.W + (long)st * C;
+    for (int j = threadIdx.x; j < C; j += 256) nx[j] = nr[j];
+    cl = ga.cls + (long)g * V;
+  }
+  __syncthreads();
+  const int s = slot[row];
+  const bool state = s >= 0 && s < S;
+  const int* cr = state ? counts + s * (long)V : nullptr;
+  const unsigned char* mr = state ? pmask + s * (long)V : nullptr;
+  const float r = state ? rep[row] : 1.f, f = state ? freq[row] : 0.f, p = state ? pres[row] : 0.f;
+  const bool vec = (V & 3) == 0 && aligned(lr, 4 * (int)sizeof(T)) && aligned(xr, 16) &&
+                   (!state || (aligned(cr, 16) && aligned(mr, 4))) && (!guided || aligned(cl, 16));
+  const int V4 = vec ? V >> 2 : 0;
+  // one branch-free loop per (state, guided) combination; the values of a row with a state are
+  // those of penalize_kernel, bit for bit
+  auto run = [&](auto st_, auto gd_) {
+    constexpr bool kState = decltype(st_)::value, kGuide = decltype(gd_)::value;
+#pragma unroll 4
+    for (int c = threadIdx.x; c < V4; c += 256) {
+      f32x4 x = ld4(lr, c);
+      if constexpr (kState) {
+        const i32x4 cn = reinterpret_cast<const i32x4*>(cr)[c];
+        const u8x4 m = reinterpret_cast<const u8x4*>(mr)[c];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] = penalized(x[e], cn[e], m[e], r, f, p);
+      }
+      if constexpr (kGuide) {
+        const i32x4 k = reinterpret_cast<const i32x4*>(cl)[c];
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if ((unsigned)k[e] >= (unsigned)C || nx[k[e]] < 0) x[e] = -INFINITY;
+      }
+      reinterpret_cast<f32x4*>(xr)[c] = x;
+    }
+    for (int i = V4 * 4 + threadIdx.x; i < V; i += 256) {
+      float x = ld(lr, i);
+      if constexpr (kState) x = penalized(x, cr[i], mr[i], r, f, p);
+      if constexpr (kGuide) {
+        const int k = cl[i];
+        if ((unsigned)k >= (unsigned)C || nx[k] < 0) x = -INFINITY;
+      }
+      xr[i] = x;
+    }
+  };
+  using yes = std::true_type;
+  using no = std::false_type;
+  if (state) {
+    if (guided) run(yes{}, yes{});
+    else run(yes{}, no{});
+  } else {
+    if (guided) run(no{}, yes{});
+    else run(no{}, no{});
+  }
+}
+
 // (value, index) arg-max over the workgroup in the order "larger value first, lower index on
 // ties"; an index of INT_MAX means no candidate.  All threads get the result.
 __device__ __forceinline__ void bargmax(float& v, int& idx, float* smv, int* smi) {
@@ -294,11 +409,15 @@ __device__ __forceinline__ void bargmax(float& v, int& idx, float* smv, int* smi
   __syncthreads();
 }
 
+// kGuided (``sample_guided`` only): -inf entries (masked tokens) are never listed (the scan is the
+// unflagged one; a round whose best entry is -inf ends the list), and thread 0 advances the row's
+// automaton state after the count increment.
+template <bool kGuided = false>
 __global__ __launch_bounds__(256) void logprob_topk_kernel(const float* __restrict__ x, const int64_t* __restrict__ toks,
                                                             const int* __restrict__ slot, const int* __restrict__ nlp,
                                                             int* __restrict__ counts, float* __restrict__ logprob,
                                                             int* __restrict__ top_ids, float* __restrict__ top_lp,
-                                                            int V, int S) {
+                                                            int V, int S, GuideArgs ga = GuideArgs{}) {
   __shared__ float sm[8];
   __shared__ float smv[4];
   __shared__ int smi[4];
@@ -350,6 +469,8 @@ __global__ __launch_bounds__(256) void logprob_topk_kernel(const float* __restri
       }
       for (int i = V4 * 4 + tid; i < V; i += 256) take(xr[i], i);
       bargmax(bv, bi, smv, smi);
+      // the best entry left is masked: so is every other one, and the list ends here
+      if (kGuided && bv == -INFINITY) bi = 0x7fffffff;
     }
     if (tid == 0) {
       const bool ok = bi != 0x7fffffff;
@@ -363,6 +484,14 @@ __global__ __launch_bounds__(256) void logprob_topk_kernel(const float* __restri
   if (tid == 0 && s >= 0 && s < S) {  // after everything above; rows of a launch never share a slot
     int* c = counts + s * (long)V + tok;
     *c = *c + 1;
+  }
+  if constexpr (kGuided) {
+    int g, gs, st, C;
+    if (tid == 0 && tok >= 0 && tok < V && guide_of(ga, row, g, gs, st, C)) {
+      const int c = ga.cls[(long)g * V + tok];
+      const int nxt = (unsigned)c < (unsigned)C ? ga.next[(long)g * ga.W + (long)st * C + c] : -1;
+      if (nxt >= 0) ga.state[gs] = nxt;  // a negative result cannot happen with a well-formed guide
+    }
   }
 }
 
@@ -438,15 +567,81 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> sample_ext(
   hipLaunchKernelGGL(sample_kernel<float>, dim3(N), dim3(256), 0, st, x.data_ptr<float>(),
                      temperature.data_ptr<float>(), top_k.data_ptr<int>(), top_p.data_ptr<float>(),
                      uniform.data_ptr<float>(), toks.data_ptr<int64_t>(), V);
-  hipLaunchKernelGGL(logprob_topk_kernel, dim3(N), dim3(256), 0, st, x.data_ptr<float>(), toks.data_ptr<int64_t>(),
+  hipLaunchKernelGGL(logprob_topk_kernel<false>, dim3(N), dim3(256), 0, st, x.data_ptr<float>(), toks.data_ptr<int64_t>(),
                      slot.data_ptr<int>(), nlp.data_ptr<int>(), counts.data_ptr<int>(), logprob.data_ptr<float>(),
-                     top_ids.data_ptr<int>(), top_lp.data_ptr<float>(), V, S);
+                     top_ids.data_ptr<int>(), top_lp.data_ptr<float>(), V, S, GuideArgs{});
+  return {toks, logprob, top_ids, top_lp};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> sample_guided(
+    const at::Tensor& logits, const at::Tensor& temperature, const at::Tensor& top_k, const at::Tensor& top_p,
+    const at::Tensor& uniform, const at::Tensor& slot, const at::Tensor& rep, const at::Tensor& freq,
+    const at::Tensor& pres, const at::Tensor& nlp, at::Tensor& counts, const at::Tensor& prompt_mask,
+    const at::Tensor& guide, const at::Tensor& gslot, const at::Tensor& guide_cls, const at::Tensor& guide_next,
+    const at::Tensor& guide_meta, at::Tensor& guide_state) {
+  LLMCTL_CHECK(logits.dim() == 2 && logits.is_contiguous(), "logits: contiguous [N, V]");
+  const int N = logits.size(0), V = logits.size(1);
+  LLMCTL_CHECK(V >= 1, "logits: V >= 1");
+  LLMCTL_CHECK(temperature.scalar_type() == at::kFloat && top_p.scalar_type() == at::kFloat &&
+                   uniform.scalar_type() == at::kFloat && top_k.scalar_type() == at::kInt,
+               "temperature/top_p/uniform fp32, top_k int32");
+  LLMCTL_CHECK(rep.scalar_type() == at::kFloat && freq.scalar_type() == at::kFloat &&
+                   pres.scalar_type() == at::kFloat && slot.scalar_type() == at::kInt && nlp.scalar_type() == at::kInt &&
+                   guide.scalar_type() == at::kInt && gslot.scalar_type() == at::kInt,
+               "rep/freq/pres fp32, slot/nlp/guide/gslot int32");
+  for (const at::Tensor* t : {&temperature, &top_k, &top_p, &uniform, &slot, &rep, &freq, &pres, &nlp, &guide, &gslot})
+    LLMCTL_CHECK(t->numel() == N && t->is_contiguous() && t->device() == logits.device(),
+                 "per-row parameter tensors must have N elements on the logits' device");
+  LLMCTL_CHECK(counts.dim() == 2 && counts.size(1) == V && counts.scalar_type() == at::kInt && counts.is_contiguous() &&
+                   counts.device() == logits.device(),
+               "counts: contiguous int32 [S, V] on the logits' device");
+  LLMCTL_CHECK(prompt_mask.dim() == 2 && prompt_mask.size(0) == counts.size(0) && prompt_mask.size(1) == V &&
+                   prompt_mask.scalar_type() == at::kByte && prompt_mask.is_contiguous() &&
+                   prompt_mask.device() == logits.device(),
+               "prompt_mask: contiguous uint8 [S, V] on the logits' device");
+  for (const at::Tensor* t : {&guide_cls, &guide_next, &guide_meta, static_cast<const at::Tensor*>(&guide_state)})
+    LLMCTL_CHECK(t->scalar_type() == at::kInt && t->is_contiguous() && t->device() == logits.device(),
+                 "guide_cls/guide_next/guide_meta/guide_state: contiguous int32 on the logits' device");
+  LLMCTL_CHECK(guide_cls.dim() == 2 && guide_cls.size(1) == V, "guide_cls: [G, V]");
+  const int G = guide_cls.size(0);
+  LLMCTL_CHECK(guide_next.dim() == 2 && guide_next.size(0) == G && guide_next.size(1) < (1LL << 31), "guide_next: [G, W]");
+  LLMCTL_CHECK(guide_meta.dim() == 2 && guide_meta.size(0) == G && guide_meta.size(1) == 2, "guide_meta: [G, 2]");
+  LLMCTL_CHECK(guide_state.dim() == 1 && guide_state.size(0) < (1LL << 31), "guide_state: [Sg]");
+  const int S = counts.size(0);
+  const c10::DeviceGuard g(logits.device());
+  auto toks = at::empty({N}, logits.options().dtype(at::kLong));
+  auto logprob = at::empty({N}, logits.options().dtype(at::kFloat));
+  auto top_ids = at::empty({N, kTopLp}, logits.options().dtype(at::kInt));
+  auto top_lp = at::empty({N, kTopLp}, logits.options().dtype(at::kFloat));
+  if (N == 0) return {toks, logprob, top_ids, top_lp};
+  auto x = at::empty({N, V}, logits.options().dtype(at::kFloat));  // the penalized and masked rows
+  const GuideArgs ga{guide.data_ptr<int>(),      gslot.data_ptr<int>(),      guide_cls.data_ptr<int>(),
+                     guide_next.data_ptr<int>(), guide_meta.data_ptr<int>(), guide_state.data_ptr<int>(),
+                     G,                          (int)guide_next.size(1),    (int)guide_state.size(0)};
+  const hipStream_t st = stream();
+  if (logits.scalar_type() == at::kBFloat16)
+    hipLaunchKernelGGL(penalize_mask_kernel<unsigned short>, dim3(N), dim3(256), 0, st, bf_ptr(logits),
+                       slot.data_ptr<int>(), rep.data_ptr<float>(), freq.data_ptr<float>(), pres.data_ptr<float>(),
+                       counts.data_ptr<int>(), prompt_mask.data_ptr<unsigned char>(), x.data_ptr<float>(), V, S, ga);
+  else if (logits.scalar_type() == at::kFloat)
+    hipLaunchKernelGGL(penalize_mask_kernel<float>, dim3(N), dim3(256), 0, st, logits.data_ptr<float>(),
+                       slot.data_ptr<int>(), rep.data_ptr<float>(), freq.data_ptr<float>(), pres.data_ptr<float>(),
+                       counts.data_ptr<int>(), prompt_mask.data_ptr<unsigned char>(), x.data_ptr<float>(), V, S, ga);
+  else
+    LLMCTL_CHECK(false, "logits must be bf16 or fp32");
+  hipLaunchKernelGGL((sample_kernel<float, true>), dim3(N), dim3(256), 0, st, x.data_ptr<float>(),
+                     temperature.data_ptr<float>(), top_k.data_ptr<int>(), top_p.data_ptr<float>(),
+                     uniform.data_ptr<float>(), toks.data_ptr<int64_t>(), V);
+  hipLaunchKernelGGL(logprob_topk_kernel<true>, dim3(N), dim3(256), 0, st, x.data_ptr<float>(),
+                     toks.data_ptr<int64_t>(), slot.data_ptr<int>(), nlp.data_ptr<int>(), counts.data_ptr<int>(),
+                     logprob.data_ptr<float>(), top_ids.data_ptr<int>(), top_lp.data_ptr<float>(), V, S, ga);
   return {toks, logprob, top_ids, top_lp};
 }
 
 TORCH_LIBRARY_IMPL(llmctl, CUDA, m) {
   m.impl("sample", &sample);
   m.impl("sample_ext", &sample_ext);
+  m.impl("sample_guided", &sample_guided);
 }
 
 }  // namespace llmctl

@@ -753,6 +753,43 @@ def sample_ext(logits, temperature, top_k, top_p, uniform, slot, rep, freq, pres
     return ref.sample_ext(logits, temperature, top_k, top_p, uniform, slot, rep, freq, pres, nlp, counts, prompt_mask)
 
 
+def sample_guided(logits, temperature, top_k, top_p, uniform, slot, rep, freq, pres, nlp, counts, prompt_mask,
+                  guide, gslot, guide_cls, guide_next, guide_meta, guide_state, check_slots: bool = True):
+    """``sample_ext`` plus a token-class automaton per guided row (semantics: ``ref.sample_guided``):
+    the row's logits are masked by its guide's current state, the draw, the logprobs and the top
+    lists run over the allowed tokens, and ``guide_state`` advances in place -- all on the device,
+    so a captured decode step keeps following the grammar with no host sync.  ``guide int32 [N]``
+    is the table slot of every row (-1: unguided), ``gslot int32 [N]`` its word of ``guide_state``.
+    Outside a capture ``check_slots`` verifies (host syncs) that state slots and ``gslot`` are in
+    range and distinct and ``guide`` is in range; a caller that owns the allocation may skip it."""
+    if use_native(logits):
+        if check_slots and not torch.cuda.is_current_stream_capturing():
+            s = slot[slot >= 0]
+            if s.numel() and (int(s.max()) >= counts.shape[0] or torch.unique(s).numel() != s.numel()):
+                raise ValueError(f"sample_guided: state slots must be distinct and below {counts.shape[0]}, "
+                                 f"got {slot.tolist()}")
+            on = guide >= 0
+            gs = gslot[on]
+            if gs.numel() and (int(gs.min()) < 0 or int(gs.max()) >= guide_state.shape[0]
+                               or torch.unique(gs).numel() != gs.numel()):
+                raise ValueError(f"sample_guided: gslot of guided rows must be distinct and below "
+                                 f"{guide_state.shape[0]}, got {gslot.tolist()}")
+            if on.any() and int(guide.max()) >= guide_cls.shape[0]:
+                raise ValueError(f"sample_guided: guide must be below {guide_cls.shape[0]}, got {guide.tolist()}")
+        toks, logprob, top_ids, top_lp = native().sample_guided(logits, temperature, top_k, top_p, uniform, slot, rep,
+                                                                 freq, pres, nlp, counts, prompt_mask, guide, gslot,
+                                                                 guide_cls, guide_next, guide_meta, guide_state)
+        return toks, logprob, top_ids, top_lp
+    return ref.sample_guided(logits, temperature, top_k, top_p, uniform, slot, rep, freq, pres, nlp, counts,
+                             prompt_mask, guide, gslot, guide_cls, guide_next, guide_meta, guide_state)
+
+
+def guide_state_reset(guide_state, gslot: int, state: int) -> None:
+    """Set the automaton state of ``gslot`` (once per admission or resumption: plain torch,
+    enqueued on the current stream)."""
+    guide_state[gslot:gslot + 1].fill_(int(state))
+
+
 def sampler_state_reset(counts, prompt_mask, slot: int, prompt_ids, output_ids) -> None:
     """Initialise slot ``slot`` of the ``sample_ext`` state from a sequence's prompt and generated
     tokens (once per admission or resumption: plain torch, enqueued on the current stream)."""
@@ -764,7 +801,7 @@ __all__ = [
     "rmsnorm", "add_rmsnorm", "layernorm", "add_layernorm", "rope_qkv", "flash_attention", "rope_flash_attention",
     "swiglu",
     "gelu", "cross_entropy", "adamw_step_", "l2norm_sq", "kv_cache_write", "paged_attention_decode",
-    "sample", "sample_ext", "sampler_state_reset", "decode_linear", "decode_linear_fp8", "decode_linear_int4", "decode_fused_ok", "decode_qkv_rope_cache", "decode_up_swiglu", "decode_attention_qkv", "up_swiglu",
+    "sample", "sample_ext", "sample_guided", "guide_state_reset", "sampler_state_reset", "decode_linear", "decode_linear_fp8", "decode_linear_int4", "decode_fused_ok", "decode_qkv_rope_cache", "decode_up_swiglu", "decode_attention_qkv", "up_swiglu",
     "decode_linear_add_rmsnorm", "rope_qkv_cache", "paged_prefill_attention", "prefill_work_list", "attn_merge_",
     "rms_rstd", "rowscale_ok", "linear_rowscale", "up_swiglu_rowscale", "linear_acc_",
     "MoEExpertTable", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",

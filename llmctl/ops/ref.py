@@ -443,6 +443,104 @@ def sample_ext(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Ten
     return toks, logprob, top_ids, top_lp
 
 
+def guide_mask(guide: torch.Tensor, gslot: torch.Tensor, guide_cls: torch.Tensor, guide_next: torch.Tensor,
+               guide_meta: torch.Tensor, guide_state: torch.Tensor) -> torch.Tensor:
+    """bool [N, V]: the tokens each row's guide allows in its current state (all True for a row
+    with ``guide = -1``)."""
+    N, V = guide.shape[0], guide_cls.shape[1]
+    ok = torch.ones(N, V, dtype=torch.bool, device=guide_cls.device)
+    for i in range(N):
+        g = int(guide[i])
+        if g < 0:
+            continue
+        C = int(guide_meta[g, 1])
+        st = int(guide_state[int(gslot[i])])
+        ok[i] = guide_next[g, st * C:(st + 1) * C][guide_cls[g].long()] >= 0
+    return ok
+
+
+def sample_guided(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
+                  uniform: torch.Tensor, slot: torch.Tensor, rep: torch.Tensor, freq: torch.Tensor, pres: torch.Tensor,
+                  nlp: torch.Tensor, counts: torch.Tensor, prompt_mask: torch.Tensor, guide: torch.Tensor,
+                  gslot: torch.Tensor, guide_cls: torch.Tensor, guide_next: torch.Tensor, guide_meta: torch.Tensor,
+                  guide_state: torch.Tensor, draw_dtype: torch.dtype = torch.float32):
+    """:func:`sample_ext` with a token-class automaton per guided row; returns the same four
+    tensors and MUTATES ``counts`` and ``guide_state``.
+
+    Per row: ``guide`` (a table slot, ``-1``: unguided) and ``gslot`` (the row's word of
+    ``guide_state int32 [Sg]``: its current automaton state; ``-1`` with ``guide = -1``).  Table slot
+    ``g`` is ``guide_cls[g] int32 [V]`` (the class of every token), ``guide_next[g] int32 [W]``
+    holding ``next[s * C_g + c]`` (``-1``: not allowed) and ``guide_meta[g] = (S_g, C_g)``.
+    Semantics (shared with ``csrc/sampling.hip``):
+
+    1. ``x`` = the penalized row of :func:`sample_ext`; for a guided row in state ``s``, ``x[v] =
+       -inf`` wherever ``next[s * C + cls[v]] < 0``.  Every state of a well-formed guide allows at
+       least one token;
+    2. the token is drawn from ``x`` by the rule of :func:`sample` with the masked entries never
+       kept: the top-k and top-p cut-offs are taken over the allowed tokens (the k-th largest
+       allowed value; the minimal descending prefix reaching ``top_p`` of the allowed mass), and
+       -- ONE CORRECTION to :func:`sample` -- an inverse-CDF result past the end (``r`` at the very
+       top, by rounding) is clamped to the last *kept* entry, not to ``V - 1``, which may be masked;
+    3. ``logprob`` and the top lists as in :func:`sample_ext`, over the masked row: the logprobs are
+       renormalised over the allowed set, ``-inf`` entries are never listed, and with fewer allowed
+       tokens than ``nlp`` the remaining entries are ``(-1, -inf)``;
+    4. ``counts[slot, tok] += 1`` as in :func:`sample_ext`, then for a guided row ``guide_state[gslot] =
+       next[s * C + cls[tok]]`` (left alone if negative, which a well-formed guide cannot give).
+       No two rows of a call share a ``gslot``; they may share a ``guide``.
+
+    ``draw_dtype``: the arithmetic of step 2 (fp32 as the kernel; fp64 to see how far summation
+    order can move an inverse-CDF boundary)."""
+    N, V = logits.shape
+    x = penalize(logits, slot, rep, freq, pres, counts, prompt_mask)
+    ok = guide_mask(guide, gslot, guide_cls, guide_next, guide_meta, guide_state)
+    x = torch.where(ok, x, torch.full_like(x, -float("inf")))
+    toks = torch.empty(N, dtype=torch.long, device=logits.device)
+    for i in range(N):
+        l = x[i].to(draw_dtype)
+        t = float(temperature[i])
+        if t <= 0:
+            toks[i] = int(torch.argmax(l))
+            continue
+        xs = l / t
+        e = torch.exp(xs - xs.max())
+        thr = -float("inf")
+        k = int(top_k[i])
+        if 0 < k < V:
+            thr = float(torch.topk(xs, k).values[-1])
+        tp = float(top_p[i])
+        if tp < 1.0:
+            sx, si = torch.sort(xs, descending=True)
+            cum = torch.cumsum(e[si], 0)
+            n = int(torch.searchsorted(cum, torch.tensor([tp * float(e.sum())], device=cum.device, dtype=cum.dtype),
+                                       right=False)[0])
+            thr = max(thr, float(sx[min(n, V - 1)]))
+        keep = (xs >= thr) & torch.isfinite(xs)
+        cum = torch.cumsum(torch.where(keep, e, torch.zeros_like(e)), 0)
+        r = float(uniform[i].to(draw_dtype)) * float(cum[-1])
+        j = int(torch.searchsorted(cum, torch.tensor([r], device=cum.device, dtype=cum.dtype), right=True)[0])
+        toks[i] = j if j < V else int(keep.nonzero()[-1])
+    lp = x.double() - torch.logsumexp(x.double(), dim=1, keepdim=True)
+    logprob = lp.gather(1, toks.view(N, 1)).view(N).float()
+    top_ids = torch.full((N, TOP_LOGPROBS), -1, dtype=torch.int32, device=logits.device)
+    top_lp = torch.full((N, TOP_LOGPROBS), -float("inf"), dtype=torch.float32, device=logits.device)
+    order = torch.sort(x, dim=1, descending=True, stable=True).indices
+    for i in range(N):
+        k = min(max(int(nlp[i]), 0), TOP_LOGPROBS, int(torch.isfinite(x[i]).sum()))
+        top_ids[i, :k] = order[i, :k].to(torch.int32)
+        top_lp[i, :k] = lp[i, order[i, :k]].float()
+        s = int(slot[i])
+        if s >= 0:
+            counts[s, int(toks[i])] += 1
+        g = int(guide[i])
+        if g >= 0:
+            C = int(guide_meta[g, 1])
+            gs = int(gslot[i])
+            nxt = int(guide_next[g, int(guide_state[gs]) * C + int(guide_cls[g, int(toks[i])])])
+            if nxt >= 0:
+                guide_state[gs] = nxt
+    return toks, logprob, top_ids, top_lp
+
+
 def sampler_state_reset(counts: torch.Tensor, prompt_mask: torch.Tensor, slot: int, prompt_ids, output_ids) -> None:
     """Slot ``slot`` of the ``sample_ext`` state as it stands after ``prompt_ids`` were given and
     ``output_ids`` generated: both rows zeroed, then the prompt's tokens marked and the generated

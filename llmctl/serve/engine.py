@@ -21,6 +21,9 @@ prompts), and sampled with a host sync per request per token.  Here:
   once per step; the only host sync per step is reading the sampled ids.  Requests with
   repetition / presence / frequency penalties or logprobs sample through ``ops.sample_ext``,
   which keeps the per-sequence token counts on the device and returns the logprobs with the ids.
+  Guided requests (regex / choice / JSON schema, ``llmctl/serve/guided.py``) sample through
+  ``ops.sample_guided``: the compiled token automaton sits in a preallocated device arena and the
+  sampler masks the logits by, and advances, the row's automaton state inside the step.
 """
 
 from __future__ import annotations
@@ -55,7 +58,7 @@ class InferenceEngine:
                  use_graphs: bool = True, seed: int = 0, pc=None, prefix_caching: bool = True,
                  tuning_cache: Optional[str] = None, perf_knobs: Optional[Dict] = None,
                  kv_cache_dtype: str = "auto", weight_dtype: str = "auto", max_loras: int = 0,
-                 max_lora_rank: int = 16):
+                 max_lora_rank: int = 16, guide_table_words: int = 1 << 18):
         from llmctl.config import knobs as perf
 
         self.knobs = perf.configure(perf_knobs)  # defaults + perf_knobs + LLMCTL_KNOBS
@@ -163,8 +166,20 @@ class InferenceEngine:
         # batches with an adapter row replay a third family, keyed (bucket, extended): the same body
         # with every projection's ``ops.LoRARows`` passed down and a static per-row ``lora_idx``
         self._graphs_lora: Dict[Tuple[int, bool], Tuple[torch.cuda.CUDAGraph, Dict[str, torch.Tensor]]] = {}
+        # batches with a guided row replay a fourth family (and the LoRA family's kind 2): the body
+        # samples with ``ops.sample_guided``.  The guides' tables live in an arena allocated on first
+        # need: G = max_batch_size table slots (shared by sequences with the same guide, reference
+        # counted) and one automaton-state word per row slot.  Addresses never change, so uploading a
+        # guide is a copy into its slot and captured graphs stay valid.
+        self._graphs_guided: Dict[int, Tuple[torch.cuda.CUDAGraph, Dict[str, torch.Tensor]]] = {}
+        self.guide_table_words = int(guide_table_words)
+        self._guide_arena: Optional[Dict[str, torch.Tensor]] = None
+        self._guide_tables: Dict[Tuple, List[int]] = {}  # guide key -> [table slot, references]
+        self._guide_table_free: List[int] = []
         self._sampler_state: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
-        self._sampler_free: List[int] = []
+        # row slots: one per running sequence that needs device-resident sampler state -- the
+        # penalties' counts row and / or the guide's state word share the index
+        self._sampler_free: List[int] = list(range(max_batch_size - 1, -1, -1))
         self._ext_step: Optional[Dict[str, np.ndarray]] = None  # the extended fields of the step being launched
         self._ext_out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None  # its logprob outputs
         self._host_lp: Optional[List] = None  # logprob rows of the last host-sampled batch
@@ -680,7 +695,9 @@ class InferenceEngine:
     _EXT = ("slot", "rep", "freq", "pres", "nlp")  # per-row inputs of ops.sample_ext, in argument order
     _EXT_OUT = ("lp", "top_ids", "top_lp")  # its logprob outputs
 
-    def _static_ext(self, nb: int, bufs: Dict) -> None:
+    _GUIDED = ("guide", "gslot")  # the further per-row inputs of ops.sample_guided
+
+    def _static_ext(self, nb: int, bufs: Dict, guided: bool = False) -> None:
         """The extended graph's additional static buffers: the per-row ``sample_ext`` parameters
         (neutral defaults: no state, no penalties, no top list) and two pinned host sets for the
         logprob outputs, flipped with ``host_toks``."""
@@ -690,6 +707,9 @@ class InferenceEngine:
         bufs["freq"] = torch.zeros(nb, dtype=torch.float32, device=d)
         bufs["pres"] = torch.zeros(nb, dtype=torch.float32, device=d)
         bufs["nlp"] = torch.zeros(nb, dtype=torch.int32, device=d)
+        if guided:  # the guided graph: table slot and state word of every row (-1: unguided)
+            bufs["guide"] = torch.full((nb,), -1, dtype=torch.int32, device=d)
+            bufs["gslot"] = torch.full((nb,), -1, dtype=torch.int32, device=d)
         W = ops.ref.TOP_LOGPROBS
         host = lambda: {"lp": torch.zeros(nb, dtype=torch.float32).pin_memory(),
                         "top_ids": torch.zeros(nb, W, dtype=torch.int32).pin_memory(),
@@ -735,7 +755,14 @@ class InferenceEngine:
         asynchronous path launches step N + 1 without reading step N's tokens first)."""
         bufs["logits"] = self._decode_body(bufs["ids"], bufs["positions"], bufs["slots"], bufs["block_tables"],
                                            bufs["ctx_lens"], bufs.get("lora_idx"))
-        if "slot" in bufs:  # the extended graph: penalties, logprobs and the state update ride in the sampler
+        if "guide" in bufs:  # the guided graph: also the guide's mask and the automaton step
+            counts, mask = self._sampler_tensors()
+            a = self._guide_arena
+            bufs["toks"], bufs["lp"], bufs["top_ids"], bufs["top_lp"] = ops.sample_guided(
+                bufs["logits"].contiguous(), bufs["temp"], bufs["topk"], bufs["topp"], bufs["u"],
+                *(bufs[k] for k in self._EXT), counts, mask, bufs["guide"], bufs["gslot"], a["cls"], a["next"],
+                a["meta"], a["state"], check_slots=False)
+        elif "slot" in bufs:  # the extended graph: penalties, logprobs and the state update ride in the sampler
             counts, mask = self._sampler_state
             bufs["toks"], bufs["lp"], bufs["top_ids"], bufs["top_lp"] = ops.sample_ext(
                 bufs["logits"].contiguous(), bufs["temp"], bufs["topk"], bufs["topp"], bufs["u"],
@@ -744,17 +771,25 @@ class InferenceEngine:
             bufs["toks"] = ops.sample(bufs["logits"].contiguous(), bufs["temp"], bufs["topk"], bufs["topp"], bufs["u"])
         bufs["ids"].copy_(bufs["toks"])
 
-    def _graph_family(self, nb: int, ext: bool, lora: bool):
-        """(dict, key) of the graph an ``nb``-row step replays: plain, extended sampler, or -- a step
-        with an adapter row -- the LoRA family, keyed (bucket, extended)."""
-        if lora:
-            return self._graphs_lora, (nb, ext)
-        return (self._graphs_ext if ext else self._graphs), nb
+    @staticmethod
+    def _sampler_kind(ext: Optional[Dict]) -> int:
+        """The sampler of a step from its extended fields: 0 plain (``ops.sample``), 1 extended
+        (``ops.sample_ext``), 2 guided (``ops.sample_guided``)."""
+        return 0 if ext is None else 2 if "guide" in ext else 1
 
-    def _capture(self, nb: int, ext: bool = False, lora: bool = False):
+    def _graph_family(self, nb: int, kind: int, lora: bool):
+        """(dict, key) of the graph an ``nb``-row step replays: plain, extended sampler, guided
+        sampler, or -- a step with an adapter row -- the LoRA family, keyed (bucket, sampler kind)."""
+        kind = int(kind)
+        if lora:
+            return self._graphs_lora, (nb, kind)
+        return (self._graphs, self._graphs_ext, self._graphs_guided)[kind], nb
+
+    def _capture(self, nb: int, ext: int = 0, lora: bool = False):
+        """``ext``: the sampler kind (0 / False plain, 1 / True extended, 2 guided)."""
         bufs = self._static(nb, lora)
         if ext:
-            self._static_ext(nb, bufs)
+            self._static_ext(nb, bufs, guided=int(ext) == 2)
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
@@ -770,9 +805,10 @@ class InferenceEngine:
     def release_graphs(self) -> None:
         """Drop the captured decode graphs (they hold the RCCL communicator's captured
         collectives: release them before ``destroy_process_group``)."""
-        if (self._graphs or self._graphs_ext or self._graphs_lora) and self.device.type == "cuda":
+        families = (self._graphs, self._graphs_ext, self._graphs_guided, self._graphs_lora)
+        if any(families) and self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
-        for graphs in (self._graphs, self._graphs_ext, self._graphs_lora):
+        for graphs in families:
             for g, _ in graphs.values():
                 g.reset()
             graphs.clear()
@@ -796,6 +832,8 @@ class InferenceEngine:
             torch.cuda.synchronize(self.device)
         self._sampler_state = None
         self._sampler_free = []
+        self._guide_arena = None
+        self._guide_tables, self._guide_table_free = {}, []
         self.kv_cache = None
         self._wq = self._wq_head = None
         self._lora = None
@@ -856,9 +894,11 @@ class InferenceEngine:
         # extended graph; its per-row penalty parameters follow the ``params_key`` rule below
         ext = self._ext_step if "temp" in plan else None
         lora = plan.get("lora")  # a step with an adapter row replays the bucket's LoRA graph
-        graphs, gkey = self._graph_family(nb, ext is not None, lora is not None)
+        kind = self._sampler_kind(ext)
+        fields = self._EXT + (self._GUIDED if kind == 2 else ())
+        graphs, gkey = self._graph_family(nb, kind, lora is not None)
         if gkey not in graphs:
-            self._capture(nb, ext is not None, lora is not None)
+            self._capture(nb, kind, lora is not None)
         g, b = graphs[gkey]
         h = b["stage"][b["flip"]]
         b["flip"] ^= 1
@@ -879,14 +919,17 @@ class InferenceEngine:
             key = (np.asarray(plan["temp"], dtype=np.float32).tobytes(), np.asarray(plan["topk"], dtype=np.int32).tobytes(),
                    np.asarray(plan["topp"], dtype=np.float32).tobytes())
             if ext is not None:
-                key += tuple(ext[k].tobytes() for k in self._EXT)
+                key += tuple(ext[k].tobytes() for k in fields)
             if ext is not None and b["params_key"] != key:
                 b["slot"].fill_(-1)
                 b["rep"].fill_(1.0)
                 b["freq"].zero_()
                 b["pres"].zero_()
                 b["nlp"].zero_()
-                for k in self._EXT:
+                if kind == 2:
+                    b["guide"].fill_(-1)
+                    b["gslot"].fill_(-1)
+                for k in fields:
                     b[k][:n].copy_(torch.from_numpy(ext[k]).to(self.device))
             if b["params_key"] != key:
                 d = self.device
@@ -946,7 +989,7 @@ class InferenceEngine:
         d = self.device
         host_lp = None
         if self._graph_ok(n):
-            graphs, gkey = self._graph_family(self._bucket(n), ext is not None, plan.get("lora") is not None)
+            graphs, gkey = self._graph_family(self._bucket(n), self._sampler_kind(ext), plan.get("lora") is not None)
             b = graphs[gkey][1]
             out = b["host_toks"][b["tflip"]]
             if want_lp:  # the logprobs ride the same pinned D2H copy as the tokens
@@ -993,10 +1036,7 @@ class InferenceEngine:
         if ext is None:
             toks = ops.sample(logits[:n].contiguous(), temp, topk, topp, u)
         else:
-            counts, mask = self._sampler_state
-            toks, lp, top_ids, top_lp = ops.sample_ext(logits[:n].contiguous(), temp, topk, topp, u,
-                                                       *(torch.from_numpy(ext[k]).to(d) for k in self._EXT), counts,
-                                                       mask, check_slots=False)
+            toks, lp, top_ids, top_lp = self._sample_ext_rows(logits[:n].contiguous(), temp, topk, topp, u, ext)
             self._ext_out = (lp, top_ids, top_lp)
         self._last_toks = toks
         return toks
@@ -1074,10 +1114,7 @@ class InferenceEngine:
         ext = self._ext_fields(seqs)
         if ext is None:
             return ops.sample(logits.contiguous(), temp, topk, topp, u)
-        counts, mask = self._sampler_state
-        toks, lp, top_ids, top_lp = ops.sample_ext(logits.contiguous(), temp, topk, topp, u,
-                                                   *(torch.from_numpy(ext[k]).to(d) for k in self._EXT), counts, mask,
-                                                   check_slots=False)
+        toks, lp, top_ids, top_lp = self._sample_ext_rows(logits.contiguous(), temp, topk, topp, u, ext)
         if any(s.params.logprobs is not None for s in seqs):  # read with the tokens (this path syncs anyway)
             self._host_lp = self._lp_rows(seqs, lp.tolist(), top_ids.tolist(), top_lp.tolist())
         return toks
@@ -1099,15 +1136,19 @@ class InferenceEngine:
         prompt and the tokens generated so far -- admission and resumption after preemption alike;
         the reset is enqueued on the engine's stream, behind any speculative row of an in-flight
         step that still writes to a recycled slot."""
-        if not any(s.params.extended for s in seqs):
+        guided = any(s.params.guided for s in seqs)
+        if not guided and not any(s.params.extended for s in seqs):
             return None
-        if self._sampler_state is None:
+        if self._sampler_state is None and (not guided or any(s.params.penalized for s in seqs)):
             S, V = self.max_batch_size, self._sampler_vocab()
             self._sampler_state = (torch.zeros(S, V, dtype=torch.int32, device=self.device),
                                    torch.zeros(S, V, dtype=torch.uint8, device=self.device))
-            self._sampler_free = list(range(S - 1, -1, -1))
             log.info("engine: sampler state for penalties: %d slots x %d tokens, %.2f MB", S, V, S * V * 5 / 1e6)
-        counts, mask = self._sampler_state
+            # guided graphs captured before hold the arena's placeholder state: capture them again
+            self._drop_graphs(lambda fam, key: fam is self._graphs_guided or (fam is self._graphs_lora and key[1] == 2))
+        if guided:
+            self._ensure_guide_arena()
+        counts, mask = self._sampler_tensors() if guided else self._sampler_state
         n = len(seqs)
         ext = {"slot": np.full(n, -1, dtype=np.int32), "rep": np.ones(n, dtype=np.float32),
                "freq": np.zeros(n, dtype=np.float32), "pres": np.zeros(n, dtype=np.float32),
@@ -1116,22 +1157,115 @@ class InferenceEngine:
             p = s.params
             if p.penalized:
                 if s.sampler_slot < 0:
-                    if not self._sampler_free:
-                        raise RuntimeError(f"no free sampler-state slot ({self.max_batch_size} penalized "
-                                           "sequences are already running)")
-                    s.sampler_slot = self._sampler_free.pop()
+                    s.sampler_slot = self._row_slot(s)
                     ops.sampler_state_reset(counts, mask, s.sampler_slot, s.prompt_ids, s.output_ids)
                 ext["slot"][i] = s.sampler_slot
                 ext["rep"][i], ext["freq"][i], ext["pres"][i] = p.repetition_penalty, p.frequency_penalty, p.presence_penalty
             if p.logprobs is not None:
                 ext["nlp"][i] = min(max(int(p.logprobs), 0), ops.ref.TOP_LOGPROBS)
+        if guided:
+            ext["guide"] = np.full(n, -1, dtype=np.int32)
+            ext["gslot"] = np.full(n, -1, dtype=np.int32)
+            for i, s in enumerate(seqs):
+                if s.params.guided:
+                    if s.guide_slot < 0:
+                        self._pin_guide(s)
+                    ext["guide"][i], ext["gslot"][i] = s.guide_table, s.guide_slot
         return ext
 
+    def _row_slot(self, seq: Sequence) -> int:
+        """The row slot of ``seq`` (its counts row and its guide-state word share the index): the one
+        it holds, or a free one."""
+        held = max(seq.sampler_slot, seq.guide_slot)
+        if held >= 0:
+            return held
+        if not self._sampler_free:
+            raise RuntimeError(f"no free sampler-state slot ({self.max_batch_size} penalized or guided "
+                               "sequences are already running)")
+        return self._sampler_free.pop()
+
     def _release_sampler_slot(self, seq: Sequence) -> None:
-        """Scheduler hook: ``seq`` finished or was preempted; its state slot returns to the free list."""
-        if seq.sampler_slot >= 0:
-            self._sampler_free.append(seq.sampler_slot)
-            seq.sampler_slot = -1
+        """Scheduler hook: ``seq`` finished or was preempted; its row slot returns to the free list
+        and its guide's table slot loses a reference."""
+        held = max(seq.sampler_slot, seq.guide_slot)
+        if held >= 0:
+            self._sampler_free.append(held)
+        seq.sampler_slot = seq.guide_slot = -1
+        if seq.guide_table >= 0:
+            ent = self._guide_tables.get(seq.guide.key)
+            if ent is not None and ent[0] == seq.guide_table:
+                ent[1] -= 1
+                if ent[1] <= 0:
+                    del self._guide_tables[seq.guide.key]
+                    self._guide_table_free.append(ent[0])
+            seq.guide_table = -1
+
+    # ------------------------------------------------------------------ guided decoding
+    def _sampler_tensors(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``counts`` / ``prompt_mask`` for ``ops.sample_guided``: the penalties' state when a
+        penalized request has made it, else the arena's one-row placeholder (every row has slot -1)."""
+        if self._sampler_state is not None:
+            return self._sampler_state
+        return self._guide_arena["counts0"], self._guide_arena["mask0"]
+
+    def _drop_graphs(self, which) -> None:
+        """Reset and forget the captured graphs for which ``which(family dict, key)`` holds."""
+        doomed = [(fam, key) for fam in (self._graphs, self._graphs_ext, self._graphs_guided, self._graphs_lora)
+                  for key in fam if which(fam, key)]
+        if doomed and self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        for fam, key in doomed:
+            fam.pop(key)[0].reset()
+
+    def _ensure_guide_arena(self) -> Dict[str, torch.Tensor]:
+        if self._guide_arena is None:
+            G, V, W, d = self.max_batch_size, self._sampler_vocab(), self.guide_table_words, self.device
+            i32 = dict(dtype=torch.int32, device=d)
+            self._guide_arena = {"cls": torch.zeros(G, V, **i32), "next": torch.full((G, W), -1, **i32),
+                                 "meta": torch.zeros(G, 2, **i32), "state": torch.zeros(G, **i32),
+                                 "counts0": torch.zeros(1, V, **i32),
+                                 "mask0": torch.zeros(1, V, dtype=torch.uint8, device=d)}
+            self._guide_table_free = list(range(G - 1, -1, -1))
+            nbytes = sum(t.numel() * t.element_size() for t in self._guide_arena.values())
+            log.info("engine: guide arena: %d table slots x (%d tokens + %d table words), %.2f MB", G, V, W,
+                     nbytes / 1e6)
+        return self._guide_arena
+
+    def _pin_guide(self, seq: Sequence) -> None:
+        """Give a guided sequence its state word and its guide a table slot (uploading the tables
+        when no running sequence holds the same guide), and set the state to where the tokens
+        generated so far lead -- admission and resumption after preemption alike.  Everything is
+        enqueued on the engine's stream, behind any step still in flight."""
+        a = self._ensure_guide_arena()
+        g = seq.guide
+        ent = self._guide_tables.get(g.key)
+        if ent is None:
+            if not self._guide_table_free:
+                raise RuntimeError(f"no free guide table slot ({self.max_batch_size} guides are in use)")
+            t = self._guide_table_free.pop()
+            S, C = g.next.shape
+            a["cls"][t].copy_(torch.from_numpy(g.cls))
+            a["next"][t, :S * C].copy_(torch.from_numpy(g.next.reshape(-1)))
+            a["meta"][t].copy_(torch.tensor([S, C], dtype=torch.int32))
+            ent = self._guide_tables[g.key] = [t, 0]
+        ent[1] += 1
+        seq.guide_table = ent[0]
+        seq.guide_slot = self._row_slot(seq)
+        ops.guide_state_reset(a["state"], seq.guide_slot, g.walk(seq.output_ids))
+
+    def _sample_ext_rows(self, logits, temp, topk, topp, u, ext: Dict[str, np.ndarray]):
+        """``ops.sample_ext`` -- or, for a step with a guided row, ``ops.sample_guided`` -- on the rows
+        of ``logits`` with the step's extended fields."""
+        d = self.device
+        fields = [torch.from_numpy(ext[k]).to(d) for k in self._EXT]
+        if "guide" not in ext:
+            counts, mask = self._sampler_state
+            return ops.sample_ext(logits, temp, topk, topp, u, *fields, counts, mask, check_slots=False)
+        counts, mask = self._sampler_tensors()
+        a = self._guide_arena
+        return ops.sample_guided(logits, temp, topk, topp, u, *fields, counts, mask,
+                                 torch.from_numpy(ext["guide"]).to(d), torch.from_numpy(ext["gslot"]).to(d),
+                                 a["cls"], a["next"], a["meta"], a["state"], check_slots=False)
 
     @staticmethod
     def _lp_rows(seqs: List[Sequence], lp: List[float], top_ids: List[List[int]], top_lp: List[List[float]]):
@@ -1151,6 +1285,14 @@ class InferenceEngine:
             if name not in self._lora_slots:
                 raise ValueError(f"unknown LoRA adapter {name!r} (loaded: {sorted(self._lora_slots) or 'none'})")
             seq.lora_slot, seq.lora_salt = self._lora_slots[name], self._lora_salt[name]
+        if getattr(params, "guided", False):  # compiled (or taken from the cache) on the caller's thread
+            from . import guided
+
+            kind, spec = guided.params_guide(params)
+            if self.tp > 1:
+                raise ValueError(f"guided_{kind} not supported with tensor parallelism > 1 (TP = {self.tp})")
+            seq.guide = guided.compile_guide(kind, spec, self.tokenizer, self._sampler_vocab(),
+                                             table_words=self.guide_table_words)
         self.scheduler.add(seq)
         return seq
 

@@ -31,7 +31,7 @@ import itertools
 import time
 from collections import deque
 from dataclasses import dataclass, field
-from typing import Any, Callable, Deque, List, Optional, Tuple
+from typing import Any, Callable, Deque, List, Optional, Tuple, Union
 
 
 @dataclass
@@ -51,6 +51,23 @@ class SamplingParams:
     frequency_penalty: float = 0.0
     logprobs: Optional[int] = None
     lora: Optional[str] = None  # name of a loaded LoRA adapter (``InferenceEngine.load_lora``)
+    # guided decoding (``llmctl/serve/guided.py``): the output is a full match of a regex, one of a
+    # list of strings, or an instance of a JSON-schema subset; at most one may be set
+    guided_regex: Optional[str] = None
+    guided_choice: Optional[List[str]] = None
+    guided_json: Optional[Union[dict, str]] = None
+
+    def __post_init__(self):
+        given = [n for n in ("guided_regex", "guided_choice", "guided_json") if getattr(self, n) is not None]
+        if len(given) > 1:
+            raise ValueError(f"at most one guide per request, got {', '.join(given)}")
+        if given and self.ignore_eos:
+            raise ValueError(f"ignore_eos cannot be combined with {given[0]} (a guided request ends with EOS)")
+
+    @property
+    def guided(self) -> bool:
+        """The output is constrained by a guide (sampled through ``ops.sample_guided``)."""
+        return self.guided_regex is not None or self.guided_choice is not None or self.guided_json is not None
 
     @property
     def penalized(self) -> bool:
@@ -93,6 +110,9 @@ class Sequence:
     block_hashes: List[bytes] = field(default_factory=list, repr=False)
     indexed_blocks: int = 0
     sampler_slot: int = -1  # row of the engine's sampler state (penalties), -1 = none held
+    guide: Any = field(default=None, repr=False)  # the compiled ``Guide`` of a guided request (add_request)
+    guide_slot: int = -1  # the sequence's word of the engine's guide_state (its automaton state), -1 = none held
+    guide_table: int = -1  # the arena slot holding its guide's tables (shared by equal guides)
     lora_slot: int = -1  # the engine's slot of ``params.lora``, resolved at add_request; -1 = base model
     lora_salt: bytes = field(default=b"", repr=False)  # seeds the prefix-cache hash chain (K/V depend on the adapter)
 

@@ -49,10 +49,44 @@ class GenerationRequest(BaseModel):
     # name of a loaded LoRA adapter (``InferenceEngine.load_lora``); a ``model`` value that equals a
     # loaded adapter's name selects it too, any other ``model`` value is served by the base
     lora: Optional[str] = None
+    # guided decoding (at most one): the completion is a full match of ``guided_regex``, one of
+    # ``guided_choice``, or an instance of the ``guided_json`` schema (a subset, see the README);
+    # OpenAI's ``response_format`` of type ``json_schema`` maps to ``guided_json``, ``text`` to nothing
+    guided_regex: Optional[str] = None
+    guided_choice: Optional[List[str]] = None
+    guided_json: Optional[Union[Dict[str, Any], str]] = None
+    response_format: Optional[Dict[str, Any]] = None
 
 
-def validate_request(req: GenerationRequest) -> None:
-    """Range checks of the extended sampling fields (``ValueError``: answered with 400)."""
+def guide_fields(req: GenerationRequest) -> Dict[str, Any]:
+    """The request's guide as ``SamplingParams`` fields (empty: unguided).  ``ValueError`` for more
+    than one guide, a guide with ``ignore_eos`` and a ``response_format`` that cannot be served."""
+    from .guided import response_format_to_guide
+
+    given = {n: getattr(req, n) for n in ("guided_regex", "guided_choice", "guided_json") if getattr(req, n) is not None}
+    rf = response_format_to_guide(req.response_format)
+    if rf is not None:
+        if given:
+            raise ValueError(f"at most one guide per request, got response_format and {', '.join(given)}")
+        given = {"guided_json": rf[1]}
+    if len(given) > 1:
+        raise ValueError(f"at most one guide per request, got {', '.join(given)}")
+    if given and req.ignore_eos:
+        raise ValueError(f"ignore_eos cannot be combined with {next(iter(given))} (a guided request ends with EOS)")
+    return given
+
+
+def validate_request(req: GenerationRequest, tokenizer=None, vocab_size: Optional[int] = None,
+                     table_words: Optional[int] = None) -> None:
+    """Range checks of the extended sampling fields and the guide (``ValueError``: answered with
+    400).  With a ``tokenizer`` the guide is compiled here (and cached for ``add_request``), so an
+    unsupported construct or a guide over the limits is refused before a stream starts."""
+    g = guide_fields(req)
+    if g and tokenizer is not None:
+        from .guided import compile_guide
+
+        (name, spec), = g.items()
+        compile_guide(name[len("guided_"):], spec, tokenizer, vocab_size, table_words=table_words)
     for name in ("presence_penalty", "frequency_penalty"):
         v = getattr(req, name)
         if not -2.0 <= v <= 2.0:
@@ -80,7 +114,8 @@ class InferenceServer:
                  max_batch_tokens: int = 8192, max_concurrent: int = 128, scheduler: str = "dynamic",
                  device: str = "auto", kv_cache_fraction: float = 0.85, block_size: int = 16, use_graphs: bool = True,
                  tensor_parallel: int = 1, engine=None, kv_cache_dtype: str = "auto", weight_dtype: str = "auto",
-                 loras: Optional[Dict[str, str]] = None, max_loras: int = 0, max_lora_rank: int = 16):
+                 loras: Optional[Dict[str, str]] = None, max_loras: int = 0, max_lora_rank: int = 16,
+                 guide_table_words: int = 1 << 18):
         from fastapi import FastAPI, HTTPException
         from fastapi.middleware.cors import CORSMiddleware
         from fastapi.responses import PlainTextResponse, StreamingResponse
@@ -91,7 +126,8 @@ class InferenceServer:
                                   max_batch_tokens=max_batch_tokens, kv_cache_fraction=kv_cache_fraction,
                                   block_size=block_size, scheduler=scheduler, use_graphs=use_graphs,
                                   kv_cache_dtype=kv_cache_dtype, weight_dtype=weight_dtype,
-                                  max_loras=max(max_loras, len(loras or {})), max_lora_rank=max_lora_rank)
+                                  max_loras=max(max_loras, len(loras or {})), max_lora_rank=max_lora_rank,
+                                  guide_table_words=guide_table_words)
         self.loras = dict(loras or {})  # adapter name -> directory, loaded when the engine starts
         if tensor_parallel != 1 and engine is None:
             raise ValueError("TP serving runs one engine per rank under torchrun: use llmctl.serve.tp "
@@ -132,7 +168,11 @@ class InferenceServer:
             if len(self.active_requests) >= self.max_concurrent:
                 raise HTTPException(status_code=503, detail="Server at capacity")
             try:
-                validate_request(req)
+                e = self.engine
+                if e is not None:
+                    validate_request(req, e.tokenizer, e._sampler_vocab(), e.guide_table_words)
+                else:
+                    validate_request(req)
                 self._lora_name(req)  # an unknown adapter is refused before a stream starts
             except ValueError as e:
                 raise HTTPException(status_code=400, detail=str(e))
@@ -241,7 +281,7 @@ class InferenceServer:
                               top_k=req.top_k, stop=stop, ignore_eos=req.ignore_eos,
                               repetition_penalty=req.repetition_penalty, presence_penalty=req.presence_penalty,
                               frequency_penalty=req.frequency_penalty, logprobs=req.logprobs,
-                              lora=self._lora_name(req))
+                              lora=self._lora_name(req), **guide_fields(req))
 
     def _logprobs_payload(self, seq) -> Dict[str, Any]:
         """``choices[0]["logprobs"]`` in the OpenAI completions shape: four lists, one entry per

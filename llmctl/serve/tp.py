@@ -173,6 +173,9 @@ class TPInferenceEngine(InferenceEngine):
             neutral = {"repetition_penalty": 1.0, "presence_penalty": 0.0, "frequency_penalty": 0.0, "logprobs": None}
             bad = [k for k, v in neutral.items() if getattr(params, k) != v]
             raise ValueError(f"{', '.join(bad)} not supported with tensor parallelism > 1 (TP = {self.tp_size})")
+        if self.tp_size > 1 and getattr(params, "guided", False):  # the automaton state lives on one rank only
+            name = next(n for n in ("guided_regex", "guided_choice", "guided_json") if getattr(params, n) is not None)
+            raise ValueError(f"{name} not supported with tensor parallelism > 1 (TP = {self.tp_size})")
         if self.tp_size > 1 and getattr(params, "lora", None) is not None:  # the stacked adapters are not sharded
             raise ValueError(f"lora not supported with tensor parallelism > 1 (TP = {self.tp_size})")
         return super().add_request(prompt_ids, params, *args, **kw)
