@@ -24,7 +24,8 @@ def run_serving_benchmark(model: str = "gpt-7b", prompt_length: int = 2048, gen_
                           lora_rank: int = 16) -> Dict[str, Any]:
     """``sampling``: extra ``SamplingParams`` fields of every request (penalties, logprobs), to
     time the extended sampler end to end (or ``guided_regex``: the guided sampler; such requests
-    end with EOS); the warm-up uses them too, so its graphs are captured before the timed run.
+    end with EOS; or ``prompt_logprobs``: every prompt is scored in its prefill, which TTFT then
+    includes); the warm-up uses them too, so its graphs are captured before the timed run.
     ``num_loras``: that many random LoRA adapters of rank ``lora_rank`` are
     loaded and request ``i`` runs on adapter ``i % num_loras`` (warm-up included)."""
     import torch

@@ -60,6 +60,8 @@ def e2e(
     lora_rank: int = typer.Option(16, help="Rank of those adapters (16, 32 or 64)"),
     guided_regex: Optional[str] = typer.Option(None, help="Guide every request by this regex (guided sampler; the "
                                                           "requests then end with EOS when the match is complete)"),
+    prompt_logprobs: Optional[int] = typer.Option(None, help="Score every request's prompt in the prefill pass, with "
+                                                             "this many alternatives per position, 0..8"),
 ) -> None:
     """End-to-end serving benchmark (TTFT p50/p99, TPOT, tokens/s).
 
@@ -75,7 +77,7 @@ def e2e(
                                 weight_dtype=weight_dtype, num_loras=num_loras, lora_rank=lora_rank,
                                 sampling={"presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty,
                                           "repetition_penalty": repetition_penalty, "logprobs": logprobs,
-                                          "guided_regex": guided_regex})
+                                          "guided_regex": guided_regex, "prompt_logprobs": prompt_logprobs})
     console.print_json(json.dumps(res))
 
 

@@ -38,6 +38,7 @@ from .functional import (
     paged_prefill_attention,
     attn_merge_,
     prefill_work_list,
+    prompt_logprobs,
     rms_rstd,
     rmsnorm,
     rope_qkv,
@@ -60,6 +61,6 @@ __all__ = [
     "flash_attention", "gelu", "kv_cache_write", "l2norm_sq", "layernorm", "paged_attention_decode",
     "paged_prefill_attention", "prefill_work_list", "attn_merge_",
     "rmsnorm", "rope_qkv", "rope_flash_attention", "rope_qkv_cache", "sample", "sample_ext", "sample_guided", "guide_state_reset", "sampler_state_reset", "swiglu", "transpose_", "up_swiglu",
-    "rms_rstd", "linear_rowscale", "up_swiglu_rowscale", "linear_acc_",
+    "prompt_logprobs", "rms_rstd", "linear_rowscale", "up_swiglu_rowscale", "linear_acc_",
     "LoRARows", "lora_delta", "MoEExpertTable", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",
 ]

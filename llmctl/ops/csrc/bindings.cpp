@@ -64,6 +64,8 @@ TORCH_LIBRARY(llmctl, m) {
   m.def("sample(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor uniform) -> Tensor");
   m.def("sample_ext(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor uniform, Tensor slot, Tensor rep, Tensor freq, Tensor pres, Tensor nlp, Tensor(a!) counts, Tensor prompt_mask) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("sample_guided(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor uniform, Tensor slot, Tensor rep, Tensor freq, Tensor pres, Tensor nlp, Tensor(a!) counts, Tensor prompt_mask, Tensor guide, Tensor gslot, Tensor guide_cls, Tensor guide_next, Tensor guide_meta, Tensor(b!) guide_state) -> (Tensor, Tensor, Tensor, Tensor)");
+  // prompt scoring (prompt_logprobs.hip): per row the target's logprob and rank and the nlp most likely tokens
+  m.def("prompt_logprobs(Tensor logits, Tensor target, Tensor nlp) -> (Tensor, Tensor, Tensor, Tensor)");
   // benchmarks / tuning (gemm_bf16.hip, hbm_stream.hip)
   m.def("gemm_bf16(Tensor a, Tensor b) -> Tensor");
   // custom all-reduce over xGMI peer memory (custom_ar.hip)

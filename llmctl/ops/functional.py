@@ -784,6 +784,16 @@ def sample_guided(logits, temperature, top_k, top_p, uniform, slot, rep, freq, p
                              prompt_mask, guide, gslot, guide_cls, guide_next, guide_meta, guide_state)
 
 
+def prompt_logprobs(logits, target, nlp):
+    """Score rows of logits against given tokens (semantics: ``ref.prompt_logprobs``): ``logits [R, V]``
+    bf16 or fp32, ``target int64 [R]``, ``nlp int32 [R]`` in 0..8 -> ``(logprob f32 [R], rank int32
+    [R], top_ids int32 [R, 8], top_lp f32 [R, 8])``.  One launch of ``csrc/prompt_logprobs.hip``
+    that reads every row once; no host sync."""
+    if use_native(logits):
+        return tuple(native().prompt_logprobs(logits.contiguous(), target.contiguous(), nlp.contiguous()))
+    return ref.prompt_logprobs(logits, target, nlp)
+
+
 def guide_state_reset(guide_state, gslot: int, state: int) -> None:
     """Set the automaton state of ``gslot`` (once per admission or resumption: plain torch,
     enqueued on the current stream)."""
@@ -801,7 +811,7 @@ __all__ = [
     "rmsnorm", "add_rmsnorm", "layernorm", "add_layernorm", "rope_qkv", "flash_attention", "rope_flash_attention",
     "swiglu",
     "gelu", "cross_entropy", "adamw_step_", "l2norm_sq", "kv_cache_write", "paged_attention_decode",
-    "sample", "sample_ext", "sample_guided", "guide_state_reset", "sampler_state_reset", "decode_linear", "decode_linear_fp8", "decode_linear_int4", "decode_fused_ok", "decode_qkv_rope_cache", "decode_up_swiglu", "decode_attention_qkv", "up_swiglu",
+    "sample", "sample_ext", "sample_guided", "prompt_logprobs", "guide_state_reset", "sampler_state_reset", "decode_linear", "decode_linear_fp8", "decode_linear_int4", "decode_fused_ok", "decode_qkv_rope_cache", "decode_up_swiglu", "decode_attention_qkv", "up_swiglu",
     "decode_linear_add_rmsnorm", "rope_qkv_cache", "paged_prefill_attention", "prefill_work_list", "attn_merge_",
     "rms_rstd", "rowscale_ok", "linear_rowscale", "up_swiglu_rowscale", "linear_acc_",
     "MoEExpertTable", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",

@@ -443,6 +443,41 @@ def sample_ext(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Ten
     return toks, logprob, top_ids, top_lp
 
 
+def prompt_logprobs(logits: torch.Tensor, target: torch.Tensor, nlp: torch.Tensor):
+    """Score every row of ``logits [R, V]`` (bf16 or fp32, finite) against ``target int64 [R]``;
+    returns ``(logprob f32 [R], rank int32 [R], top_ids int32 [R, 8], top_lp f32 [R, 8])``.
+    Semantics (shared with ``csrc/prompt_logprobs.hip``), in fp64 internally:
+
+    1. ``logprob[r] = x[r, target[r]] - logsumexp(x[r])`` over the raw row;
+    2. ``rank[r]``: the 1-based position of the target in the row's stable descending order (larger
+       value first, lower index on ties -- the order of :func:`sample_ext`'s lists), so ``rank <=
+       nlp`` exactly when the target is listed;
+    3. the first ``nlp[r]`` (0..8, at most V) entries of that order as ``(id, logprob)``; the rest
+       of the lists hold id ``-1`` and logprob ``-inf``.  A listed target's entry equals
+       ``logprob[r]`` bit for bit;
+    4. ``target[r]`` outside ``0..V-1``: ``logprob = NaN``, ``rank = 0``; the lists are produced."""
+    R, V = logits.shape
+    dev = logits.device
+    x = logits.double()
+    lp = x - torch.logsumexp(x, dim=1, keepdim=True)
+    t = target.to(dev).long()
+    ok = (t >= 0) & (t < V)
+    tc = t.clamp(0, V - 1).view(R, 1)
+    xt = x.gather(1, tc)
+    idx = torch.arange(V, device=dev).view(1, V)
+    ahead = ((x > xt) | ((x == xt) & (idx < tc))).sum(dim=1)
+    logprob = torch.where(ok, lp.gather(1, tc).view(R).float(), torch.full((R,), float("nan"), device=dev))
+    rank = torch.where(ok, ahead + 1, torch.zeros_like(ahead)).to(torch.int32)
+    W = min(TOP_LOGPROBS, V)
+    order = torch.sort(x, dim=1, descending=True, stable=True).indices[:, :W]  # stable: lowest index first on ties
+    keep = torch.arange(W, device=dev).view(1, W) < nlp.to(dev).long().clamp(0, TOP_LOGPROBS).view(R, 1)
+    top_ids = torch.full((R, TOP_LOGPROBS), -1, dtype=torch.int32, device=dev)
+    top_lp = torch.full((R, TOP_LOGPROBS), -float("inf"), dtype=torch.float32, device=dev)
+    top_ids[:, :W] = torch.where(keep, order, torch.full_like(order, -1)).to(torch.int32)
+    top_lp[:, :W] = torch.where(keep, lp.gather(1, order).float(), top_lp[:, :W])
+    return logprob, rank, top_ids, top_lp
+
+
 def guide_mask(guide: torch.Tensor, gslot: torch.Tensor, guide_cls: torch.Tensor, guide_next: torch.Tensor,
                guide_meta: torch.Tensor, guide_state: torch.Tensor) -> torch.Tensor:
     """bool [N, V]: the tokens each row's guide allows in its current state (all True for a row

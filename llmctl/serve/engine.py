@@ -12,7 +12,9 @@ prompts), and sampled with a host sync per request per token.  Here:
   attend through ``paged_prefill_attention`` (csrc/paged_prefill.hip): every query reads its
   keys from the block table, so a cached prefix (earlier chunk, prefix-cache hit, resumed
   sequence) and the chunk itself are one key range.  Logits are taken only at the last token
-  of chunks that complete a sequence's known tokens;
+  of chunks that complete a sequence's known tokens -- and, for requests that score their prompt
+  (``SamplingParams.prompt_logprobs``), at the prompt rows still to score, in tiles that go
+  through ``ops.prompt_logprobs`` (the next token's logprob, rank and top list per row);
 * decode: one token per running sequence; per layer ``rope_qkv`` (explicit positions) ->
   ``kv_cache_write`` -> ``paged_attention_decode`` (block tables, GQA) -> o-proj -> MLP;
   the whole decode step (embedding .. lm_head) is captured once per batch-size bucket in
@@ -183,6 +185,11 @@ class InferenceEngine:
         self._ext_step: Optional[Dict[str, np.ndarray]] = None  # the extended fields of the step being launched
         self._ext_out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None  # its logprob outputs
         self._host_lp: Optional[List] = None  # logprob rows of the last host-sampled batch
+        # prompt scoring (``SamplingParams.prompt_logprobs``): the logits of at most SCORE_TILE prompt
+        # rows at a time, [SCORE_TILE, V] in the model dtype (64 MB at V = 32000), allocated on
+        # first need; steps without a scoring row never touch either
+        self._score_scratch: Optional[torch.Tensor] = None
+        self._score_out: Optional[Tuple] = None  # (segments, host results, event) of the step just run
         self.scheduler.on_release = self._release_sampler_slot
         # sampling uniforms come from the host (one H2D copy with the step's other inputs), so
         # in-graph sampling and the eager path draw the same stream
@@ -392,14 +399,28 @@ class InferenceEngine:
     def prefill_plan(self, chunks: List[PrefillChunk]) -> Dict:
         """Host-side description of a (chunked, packed) prefill step — what TP ranks receive."""
         ids, pos, slots, cu, ctx, last = [], [], [], [0], [], []
+        score = None
         for i, c in enumerate(chunks):
             toks = c.seq.all_ids
             ids.extend(toks[c.start:c.start + c.count])
             pos.extend(range(c.start, c.start + c.count))
             slots.append(np.asarray(self.kv.slots(c.seq.seq_id, c.start, c.count), dtype=np.int64))
+            if c.seq.score_pending:
+                # rows still to score: prompt positions from the first unscored one, short of the
+                # prompt's last (it has no target); the target of position p is prompt_ids[p + 1],
+                # at a chunk's last row the next chunk's first token.  Rows of generated tokens (a
+                # sequence resumed after preemption) lie past the prompt and are never scored.
+                s = c.seq
+                p0, p1 = max(c.start, len(s.prompt_logprobs) - 1), min(c.start + c.count, len(s.prompt_ids) - 1)
+                if p0 < p1:
+                    score = score or {"rows": [], "targets": [], "nlp": [], "segs": []}
+                    score["rows"].extend(range(cu[-1] + p0 - c.start, cu[-1] + p1 - c.start))
+                    score["targets"].extend(s.prompt_ids[p0 + 1:p1 + 1])
+                    score["nlp"].extend([int(s.params.prompt_logprobs)] * (p1 - p0))
+                    score["segs"].append((i, p1 - p0))
             cu.append(cu[-1] + c.count)
             ctx.append(c.start + c.count)
-            if c.final:
+            if c.samples:
                 last.append(cu[-1] - 1)
         bt = np.asarray(self.kv.block_tables([c.seq.seq_id for c in chunks], self.max_blocks_per_seq))
         # every chunk is a whole fresh prompt (no cached prefix): its keys are exactly the chunk's
@@ -408,6 +429,8 @@ class InferenceEngine:
         doc = np.repeat(np.asarray(cu[:-1], dtype=np.int32), np.diff(cu)) if fresh else None
         lora = [c.seq.lora_slot for c in chunks]
         extra = {"lora": lora} if any(s >= 0 for s in lora) else {}  # adapter slot per chunk
+        if score is not None:  # only a step with rows to score carries the key
+            extra["score"] = score
         return {**extra, "op": "prefill", "ids": np.asarray(ids, dtype=np.int64), "pos": np.asarray(pos, dtype=np.int32),
                 "slots": np.concatenate(slots) if slots else np.zeros(0, dtype=np.int64), "cu": cu, "ctx": ctx,
                 "bt": bt, "last": last, "work": ops.prefill_work_list(cu), "doc": doc}
@@ -449,6 +472,8 @@ class InferenceEngine:
         if self._norm_fold_ok(T, sel):
             h = self._prefill_layers_folded(x, pos, slots, fa, doc, bt, cu, ctx, work)
             self.stats["prefill_tokens"] += T
+            if plan.get("score") is not None:
+                self._score_rows(plan["score"], h, None)
             if not plan["last"]:
                 return torch.empty(0, self.cfg.vocab_size, device=d, dtype=h.dtype)
             hl = h.index_select(0, torch.tensor(plan["last"], device=d))
@@ -471,6 +496,8 @@ class InferenceEngine:
             xn, res = self._norm(layer, a, res, "mlp")
             x = self._mlp(layer, xn, li, sel)
         self.stats["prefill_tokens"] += T
+        if plan.get("score") is not None:
+            self._score_rows(plan["score"], x, res)
         if not plan["last"]:
             return torch.empty(0, self.cfg.vocab_size, device=d, dtype=x.dtype)
         last = torch.tensor(plan["last"], device=d)
@@ -538,12 +565,95 @@ class InferenceEngine:
         self.stats["prefill_tokens"] += Tp
         self.stats["decode_tokens"] += Td
         self.stats["mixed_steps"] = self.stats.get("mixed_steps", 0) + 1
+        if pp.get("score") is not None:  # the chunks' rows come first: the plan's row numbers hold
+            self._score_rows(pp["score"], x, res)
         rows = torch.tensor(list(pp["last"]) + list(range(Tp, Tp + Td)), device=d)
         return self._final(x.index_select(0, rows), res.index_select(0, rows))
 
     def _mixed_ok(self) -> bool:
         """Knob ``mixed_steps`` off runs a step's decode and prefill as two forwards (A/B)."""
         return self.knobs.mixed_steps
+
+    # ------------------------------------------------------------------ prompt scoring
+    SCORE_TILE = 1024  # prompt rows whose logits exist at a time: the scratch is SCORE_TILE x V
+
+    def _score_rows(self, sc: Dict, x: torch.Tensor, res: Optional[torch.Tensor]) -> None:
+        """Score a prefill (or mixed) step's rows ``sc["rows"]`` against ``sc["targets"]``: final norm
+        -> vocabulary projection as a many-row library GEMM into the logits scratch ->
+        ``ops.prompt_logprobs``, in tiles of ``SCORE_TILE`` rows.  ``x`` / ``res``: the last layer's
+        output and the residual stream; ``res`` None: ``x`` is the folded prefill's residual stream,
+        with only the final RMSNorm left.  The raw logits are scored: no temperature, penalty or
+        guide.  The results leave in one D2H copy (pinned on the GPU) and are read by
+        :meth:`_finish_scores`, where the step's tokens are read."""
+        d, m, eps = self.device, self.model, self.cfg.layer_norm_eps
+        n, W = len(sc["rows"]), ops.ref.TOP_LOGPROBS
+        rows = torch.tensor(sc["rows"], dtype=torch.long).to(d, non_blocking=True)
+        target = torch.tensor(sc["targets"], dtype=torch.long).to(d, non_blocking=True)
+        nlp = torch.tensor(sc["nlp"], dtype=torch.int32).to(d, non_blocking=True)
+        w = m.head_weight()
+        if self._score_scratch is None:  # on first need, as the sampler state is
+            self._score_scratch = torch.empty(self.SCORE_TILE, w.shape[0], dtype=x.dtype, device=d)
+            log.info("engine: prompt-logprob logits scratch: %d rows x %d tokens, %.2f MB", self.SCORE_TILE, w.shape[0],
+                     self._score_scratch.numel() * self._score_scratch.element_size() / 1e6)
+        out = torch.empty(n, 2 + 2 * W, dtype=torch.int32, device=d)  # logprob | rank | top ids | top logprobs
+        for r0 in range(0, n, self.SCORE_TILE):
+            r = rows[r0:r0 + self.SCORE_TILE]
+            if res is None:
+                xn = ops.rmsnorm(x.index_select(0, r), m.final_norm_w, eps)
+            elif m.final_norm_b is not None:
+                xn, _ = ops.add_layernorm(x.index_select(0, r), res.index_select(0, r), m.final_norm_w, m.final_norm_b, eps)
+            else:
+                xn, _ = ops.add_rmsnorm(x.index_select(0, r), res.index_select(0, r), m.final_norm_w, eps)
+            logits = torch.mm(xn, w.t(), out=self._score_scratch[:r.shape[0]])
+            lp, rank, top_ids, top_lp = ops.prompt_logprobs(logits, target[r0:r0 + self.SCORE_TILE],
+                                                            nlp[r0:r0 + self.SCORE_TILE])
+            o = out[r0:r0 + r.shape[0]]
+            o[:, 0] = lp.view(torch.int32)
+            o[:, 1] = rank
+            o[:, 2:2 + W] = top_ids
+            o[:, 2 + W:] = top_lp.view(torch.int32)
+        ev = None
+        if d.type == "cuda":
+            host = torch.empty(n, 2 + 2 * W, dtype=torch.int32).pin_memory()
+            host.copy_(out, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        else:
+            host = out
+        self._score_out = (sc["segs"], host, ev)
+
+    def _finish_scores(self, chunks: List[PrefillChunk]) -> None:
+        """Append the scores of the step just run to their sequences (before any token of the step
+        is appended: ``on_token`` may read them)."""
+        so, self._score_out = self._score_out, None
+        if so is None:
+            return
+        segs, host, ev = so
+        if ev is not None:
+            ev.synchronize()
+        W = ops.ref.TOP_LOGPROBS
+        a = host.numpy()
+        f = a.view(np.float32)
+        lp, rank, ids, tlp = f[:, 0].tolist(), a[:, 1].tolist(), a[:, 2:2 + W].tolist(), f[:, 2 + W:].tolist()
+        r = 0
+        for ci, cnt in segs:
+            seq = chunks[ci].seq
+            for j in range(r, r + cnt):
+                seq.prompt_logprobs.append(lp[j])
+                seq.prompt_ranks.append(rank[j])
+                seq.prompt_top_logprobs.append([(t, v) for t, v in zip(ids[j], tlp[j]) if t >= 0])
+            r += cnt
+
+    def _finish_score_only(self, chunks: List[PrefillChunk]) -> None:
+        """Requests that only score their prompt (``max_tokens = 0``) end with their last chunk."""
+        for c in chunks:
+            if c.final and c.seq.score_only and c.seq.status == "running":
+                self.scheduler.finish(c.seq, "length")
+
+    def score(self, prompts: List[List[int]], top: int = 0, lora: Optional[str] = None) -> List[Sequence]:
+        """Score ``prompts`` and generate nothing: the finished sequences carry ``prompt_logprobs``,
+        ``prompt_ranks`` and ``prompt_top_logprobs`` (``top`` alternatives per position)."""
+        return self.generate(prompts, SamplingParams(max_tokens=0, prompt_logprobs=top, lora=lora))
 
     # ------------------------------------------------------------------ decode
     def _fused_decode(self, n: int = 1) -> bool:
@@ -831,6 +941,7 @@ class InferenceEngine:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         self._sampler_state = None
+        self._score_scratch = self._score_out = None
         self._sampler_free = []
         self._guide_arena = None
         self._guide_tables, self._guide_table_free = {}, []
@@ -1285,6 +1396,10 @@ class InferenceEngine:
             if name not in self._lora_slots:
                 raise ValueError(f"unknown LoRA adapter {name!r} (loaded: {sorted(self._lora_slots) or 'none'})")
             seq.lora_slot, seq.lora_salt = self._lora_slots[name], self._lora_salt[name]
+        if getattr(params, "prompt_logprobs", None) is not None:
+            if self.tp > 1:  # the vocabulary projection is sharded and the plan channel carries no targets
+                raise ValueError(f"prompt_logprobs not supported with tensor parallelism > 1 (TP = {self.tp})")
+            seq.prompt_logprobs, seq.prompt_ranks, seq.prompt_top_logprobs = [None], [None], [None]
         if getattr(params, "guided", False):  # compiled (or taken from the cache) on the caller's thread
             from . import guided
 
@@ -1446,13 +1561,15 @@ class InferenceEngine:
         out = self.scheduler.schedule()
         if out.decode and out.prefill and self._mixed_ok():
             logits = self.mixed(out.prefill, out.decode)
-            final = [c.seq for c in out.prefill if c.final]
+            final = [c.seq for c in out.prefill if c.samples]
             toks = self.sample(logits, final + list(out.decode))
             lps = self._take_host_lp()
+            self._finish_scores(out.prefill)
             for c in out.prefill:
                 self.scheduler.computed(c.seq, c.count)
                 self.stats["prefix_hit_tokens"] = self.stats.get("prefix_hit_tokens", 0) + (
                     c.seq.cached_tokens if c.start == c.seq.cached_tokens else 0)
+            self._finish_score_only(out.prefill)
             for seq in out.decode:
                 self.scheduler.computed(seq, 1)
             for i, (seq, tok) in enumerate(zip(final + list(out.decode), toks)):
@@ -1480,11 +1597,13 @@ class InferenceEngine:
                 produced += 1
         if out.prefill:
             logits = self.prefill(out.prefill)
-            final = [c.seq for c in out.prefill if c.final]
+            final = [c.seq for c in out.prefill if c.samples]
+            self._finish_scores(out.prefill)
             for c in out.prefill:
                 self.scheduler.computed(c.seq, c.count)
                 self.stats["prefix_hit_tokens"] = self.stats.get("prefix_hit_tokens", 0) + (
                     c.seq.cached_tokens if c.start == c.seq.cached_tokens else 0)
+            self._finish_score_only(out.prefill)
             if final:
                 toks = self.sample(logits, final)
                 lps = self._take_host_lp()

@@ -56,8 +56,16 @@ class SamplingParams:
     guided_regex: Optional[str] = None
     guided_choice: Optional[List[str]] = None
     guided_json: Optional[Union[dict, str]] = None
+    # score the prompt in the prefill pass (``ops.prompt_logprobs``): every prompt token's logprob
+    # and rank given the tokens before it, with the ``prompt_logprobs`` (0..8) most likely
+    # alternatives.  Only with it may ``max_tokens`` be 0: the request is scored and generates nothing
+    prompt_logprobs: Optional[int] = None
 
     def __post_init__(self):
+        if self.prompt_logprobs is not None and not 0 <= int(self.prompt_logprobs) <= 8:
+            raise ValueError(f"prompt_logprobs must be in 0..8, got {self.prompt_logprobs}")
+        if self.max_tokens < 1 and self.prompt_logprobs is None:
+            raise ValueError(f"max_tokens must be at least 1 (0 only together with prompt_logprobs), got {self.max_tokens}")
         given = [n for n in ("guided_regex", "guided_choice", "guided_json") if getattr(self, n) is not None]
         if len(given) > 1:
             raise ValueError(f"at most one guide per request, got {', '.join(given)}")
@@ -115,6 +123,23 @@ class Sequence:
     guide_table: int = -1  # the arena slot holding its guide's tables (shared by equal guides)
     lora_slot: int = -1  # the engine's slot of ``params.lora``, resolved at add_request; -1 = base model
     lora_salt: bytes = field(default=b"", repr=False)  # seeds the prefix-cache hash chain (K/V depend on the adapter)
+    # with ``params.prompt_logprobs`` set: one entry per prompt position once the prompt is prefilled
+    # (complete before the first generated token is appended).  Entry 0 is None (nothing precedes
+    # it); entry i is the logprob / 1-based rank of ``prompt_ids[i]`` after ``prompt_ids[:i]`` and the
+    # ``prompt_logprobs`` most likely ``(token id, logprob)`` pairs there, descending
+    prompt_logprobs: List[Optional[float]] = field(default_factory=list)
+    prompt_ranks: List[Optional[int]] = field(default_factory=list)
+    prompt_top_logprobs: List[Optional[List[Tuple[int, float]]]] = field(default_factory=list)
+
+    @property
+    def score_pending(self) -> bool:
+        """Prompt positions are still to be scored (their rows must be computed, not re-attached)."""
+        return self.params.prompt_logprobs is not None and len(self.prompt_logprobs) < len(self.prompt_ids)
+
+    @property
+    def score_only(self) -> bool:
+        """Scored, never sampled: ``max_tokens = 0``."""
+        return self.params.prompt_logprobs is not None and self.params.max_tokens < 1
 
     @property
     def all_ids(self) -> List[int]:
@@ -139,6 +164,10 @@ class PrefillChunk:
     @property
     def final(self) -> bool:  # the chunk reaches the sequence's last known token: sample after it
         return self.start + self.count == self.seq.num_tokens
+
+    @property
+    def samples(self) -> bool:  # ... unless the request only scores its prompt (max_tokens = 0)
+        return self.final and not self.seq.score_only
 
 
 @dataclass
@@ -211,6 +240,13 @@ class ContinuousBatchScheduler:
         takes its references, so the reservation must not evict them."""
         n = seq.num_tokens  # a resumed sequence also re-covers its generated tokens
         prefix = self.prefix_cache.match(seq.all_ids, salt=seq.lora_salt) if self.prefix_cache is not None else []
+        if prefix and seq.score_pending:
+            # a scoring sequence computes every prompt position it has not scored yet: position p
+            # yields entry p + 1, so the entries it holds cover positions 0 .. len - 2 (none on first
+            # admission, what was scored before a preemption afterwards)
+            keep = max(len(seq.prompt_logprobs) - 1, 0) // self.block_size
+            self.prefix_cache.stats["hit_tokens"] -= max(len(prefix) - keep, 0) * self.block_size
+            prefix = prefix[:keep]
         need = self.kv.blocks_needed(n + self.kv_block_size()) - len(prefix)
         if not self._reserve(need, protect=prefix):
             return False

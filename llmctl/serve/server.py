@@ -56,6 +56,20 @@ class GenerationRequest(BaseModel):
     guided_choice: Optional[List[str]] = None
     guided_json: Optional[Union[Dict[str, Any], str]] = None
     response_format: Optional[Dict[str, Any]] = None
+    # prompt scoring, in the prefill pass.  OpenAI form: ``echo`` with ``logprobs = k`` returns the
+    # prompt's text and tokens in front of the completion's, each prompt token with its logprob and
+    # the k most likely alternatives.  vLLM form: ``prompt_logprobs = k`` adds
+    # ``choices[0].prompt_logprobs``.  Only with either may ``max_tokens`` be 0 (score, generate
+    # nothing).  ``echo`` without ``logprobs`` only prepends the prompt text.  Not with ``stream``.
+    echo: bool = False
+    prompt_logprobs: Optional[int] = None
+
+
+def prompt_logprobs_of(req: GenerationRequest) -> Optional[int]:
+    """The ``SamplingParams.prompt_logprobs`` a request asks for: its ``prompt_logprobs`` field, or
+    ``logprobs`` under ``echo`` (the larger of the two when both are given); None: no scoring."""
+    ks = [k for k in (req.prompt_logprobs, req.logprobs if req.echo else None) if k is not None]
+    return max(ks) if ks else None
 
 
 def guide_fields(req: GenerationRequest) -> Dict[str, Any]:
@@ -95,6 +109,10 @@ def validate_request(req: GenerationRequest, tokenizer=None, vocab_size: Optiona
         raise ValueError(f"repetition_penalty must be in (0, 10], got {req.repetition_penalty}")
     if req.logprobs is not None and not 0 <= req.logprobs <= 8:
         raise ValueError(f"logprobs must be in 0..8, got {req.logprobs}")
+    if req.prompt_logprobs is not None and not 0 <= req.prompt_logprobs <= 8:
+        raise ValueError(f"prompt_logprobs must be in 0..8, got {req.prompt_logprobs}")
+    if req.stream and (req.echo or req.prompt_logprobs is not None):
+        raise ValueError(f"{'echo' if req.echo else 'prompt_logprobs'} is not supported with stream=true")
 
 
 class GenerationResponse(BaseModel):
@@ -174,6 +192,9 @@ class InferenceServer:
                 else:
                     validate_request(req)
                 self._lora_name(req)  # an unknown adapter is refused before a stream starts
+                if e is not None and e.tp > 1 and prompt_logprobs_of(req) is not None:
+                    name = "prompt_logprobs" if req.prompt_logprobs is not None else "echo with logprobs (prompt_logprobs)"
+                    raise ValueError(f"{name} not supported with tensor parallelism > 1 (TP = {e.tp})")
             except ValueError as e:
                 raise HTTPException(status_code=400, detail=str(e))
             if req.stream:
@@ -277,7 +298,9 @@ class InferenceServer:
         from .scheduler import SamplingParams
 
         stop = [req.stop] if isinstance(req.stop, str) else (req.stop or [])
-        return SamplingParams(max_tokens=max(1, req.max_tokens), temperature=req.temperature, top_p=req.top_p,
+        plp = prompt_logprobs_of(req)  # only a scoring request may generate nothing
+        return SamplingParams(max_tokens=max(0 if plp is not None else 1, req.max_tokens), prompt_logprobs=plp,
+                              temperature=req.temperature, top_p=req.top_p,
                               top_k=req.top_k, stop=stop, ignore_eos=req.ignore_eos,
                               repetition_penalty=req.repetition_penalty, presence_penalty=req.presence_penalty,
                               frequency_penalty=req.frequency_penalty, logprobs=req.logprobs,
@@ -290,6 +313,38 @@ class InferenceServer:
         return {"tokens": [dec([t]) for t in seq.output_ids], "token_ids": list(seq.output_ids),
                 "token_logprobs": list(seq.output_logprobs),
                 "top_logprobs": [{dec([t]): v for t, v in top} for top in seq.output_top_logprobs]}
+
+    def _echo_logprobs_payload(self, seq) -> Dict[str, Any]:
+        """``choices[0]["logprobs"]`` of an ``echo`` request: the prompt tokens, then the generated
+        ones.  The first prompt token has no logprob (``null``); ``text_offset`` is every token's
+        offset in ``choices[0].text``."""
+        dec = self.engine.tokenizer.decode
+        k = seq.params.logprobs
+        ids = list(seq.prompt_ids) + list(seq.output_ids)
+        toks = [dec([t]) for t in ids]
+        tops = [None if top is None else {dec([t]): v for t, v in top[:k]} for top in seq.prompt_top_logprobs]
+        offs, at = [], 0
+        for t in toks:
+            offs.append(at)
+            at += len(t)
+        return {"tokens": toks, "token_ids": ids, "token_logprobs": list(seq.prompt_logprobs) + list(seq.output_logprobs),
+                "top_logprobs": tops + [{dec([t]): v for t, v in top} for top in seq.output_top_logprobs],
+                "text_offset": offs}
+
+    def _prompt_logprobs_payload(self, seq, k: int) -> List[Optional[Dict[str, Any]]]:
+        """``choices[0]["prompt_logprobs"]`` (the vLLM shape): per prompt position ``null`` (the
+        first) or token id (a string) -> ``{logprob, rank, decoded_token}`` for the prompt token and
+        the ``k`` most likely alternatives."""
+        dec = self.engine.tokenizer.decode
+        out: List[Optional[Dict[str, Any]]] = []
+        for tok, lp, rank, top in zip(seq.prompt_ids, seq.prompt_logprobs, seq.prompt_ranks, seq.prompt_top_logprobs):
+            if lp is None:
+                out.append(None)
+                continue
+            ent = {str(t): {"logprob": v, "rank": i + 1, "decoded_token": dec([t])} for i, (t, v) in enumerate(top[:k])}
+            ent[str(tok)] = {"logprob": lp, "rank": rank, "decoded_token": dec([tok])}
+            out.append(ent)
+        return out
 
     def _encode(self, prompt) -> List[int]:
         if isinstance(prompt, list):
@@ -326,9 +381,13 @@ class InferenceServer:
         self.obs.record_inference_request(lat, ttft=ttft, tpot=tpot)
         self.health.record_inference_request(lat, success=not str(seq.finish_reason).startswith("error"))
         usage = {"prompt_tokens": len(ids), "completion_tokens": n, "total_tokens": len(ids) + n}
+        if req.echo:  # the prompt's text in front of the completion's
+            text = self.engine.tokenizer.decode(list(seq.prompt_ids)) + text
         choice = {"index": 0, "text": text, "finish_reason": seq.finish_reason}
         if req.logprobs is not None:
-            choice["logprobs"] = self._logprobs_payload(seq)
+            choice["logprobs"] = self._echo_logprobs_payload(seq) if req.echo else self._logprobs_payload(seq)
+        if req.prompt_logprobs is not None:
+            choice["prompt_logprobs"] = self._prompt_logprobs_payload(seq, req.prompt_logprobs)
         return GenerationResponse(id=rid, text=text, finish_reason=seq.finish_reason or "stop", usage=usage,
                                   created=int(t0), model=self.model_name,
                                   choices=[choice],
