@@ -21,7 +21,7 @@ def run_serving_benchmark(model: str = "gpt-7b", prompt_length: int = 2048, gen_
                           seed: int = 0, warmup: bool = True, scheduler: str = "dynamic",
                           kv_cache_dtype: str = "auto", weight_dtype: str = "auto",
                           sampling: Optional[Dict[str, Any]] = None, num_loras: int = 0,
-                          lora_rank: int = 16) -> Dict[str, Any]:
+                          lora_rank: int = 16, weight_max_rows: int = 16) -> Dict[str, Any]:
     """``sampling``: extra ``SamplingParams`` fields of every request (penalties, logprobs), to
     time the extended sampler end to end (or ``guided_regex``: the guided sampler; such requests
     end with EOS; or ``prompt_logprobs``: every prompt is scored in its prefill, which TTFT then
@@ -39,7 +39,8 @@ def run_serving_benchmark(model: str = "gpt-7b", prompt_length: int = 2048, gen_
                                                                    4096 if scheduler == "prefill_first" else 8192),
                           max_model_len=max_len,
                           use_graphs=use_graphs, seed=seed, scheduler=scheduler, kv_cache_dtype=kv_cache_dtype,
-                          weight_dtype=weight_dtype, max_loras=num_loras, max_lora_rank=lora_rank)
+                          weight_dtype=weight_dtype, weight_max_rows=weight_max_rows, max_loras=num_loras,
+                          max_lora_rank=lora_rank)
     names = []
     if num_loras > 0:
         from llmctl.serve.lora import random_adapter

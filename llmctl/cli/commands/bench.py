@@ -52,6 +52,7 @@ def e2e(
                                                                  "for prefill_first, 8192 otherwise)"),
     kv_cache_dtype: str = typer.Option("auto", help="KV cache element: auto (model dtype) | fp8 (e4m3fn)"),
     weight_dtype: str = typer.Option("auto", help="Decode projection weights: auto (model dtype) | fp8 (e4m3fn, row scales) | int4 (group-128 scales)"),
+    weight_max_rows: int = typer.Option(16, help="Most decode rows that stream the fp8 / int4 copies: 16 | 32 | 64"),
     presence_penalty: float = typer.Option(0.0, help="Presence penalty of every request (extended sampler)"),
     frequency_penalty: float = typer.Option(0.0, help="Frequency penalty of every request (extended sampler)"),
     repetition_penalty: float = typer.Option(1.0, help="Repetition penalty of every request (extended sampler)"),
@@ -74,7 +75,7 @@ def e2e(
     res = run_serving_benchmark(model=model, prompt_length=prompt_length, gen_length=gen_length, qps=qps,
                                 num_requests=num_requests, max_batch_size=max_batch_size, device=device,
                                 scheduler=scheduler, max_batch_tokens=max_batch_tokens, kv_cache_dtype=kv_cache_dtype,
-                                weight_dtype=weight_dtype, num_loras=num_loras, lora_rank=lora_rank,
+                                weight_dtype=weight_dtype, weight_max_rows=weight_max_rows, num_loras=num_loras, lora_rank=lora_rank,
                                 sampling={"presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty,
                                           "repetition_penalty": repetition_penalty, "logprobs": logprobs,
                                           "guided_regex": guided_regex, "prompt_logprobs": prompt_logprobs})

@@ -36,6 +36,8 @@ def start(
     weight_dtype: str = typer.Option("auto", help="Decode projection weights: auto (the model dtype), fp8 (OCP "
                                                   "e4m3fn, per-row scales) or int4 (group-128 scales, W4A16); "
                                                   "prefill keeps the model dtype"),
+    weight_max_rows: int = typer.Option(16, help="Most decode rows per step that stream the fp8 / int4 copies: 16, "
+                                                 "32 or 64 (above it the step streams the bf16 weights)"),
     lora: Optional[List[str]] = typer.Option(None, "--lora", help="NAME=PATH of a LoRA adapter directory to serve "
                                                                    "under NAME (repeatable)"),
     max_loras: int = typer.Option(0, help="Resident LoRA adapter slots (at least the number of --lora)"),
@@ -79,14 +81,15 @@ def start(
                "--max-batch-size", str(max_batch_size), "--max-batch-tokens", str(max_batch_tokens),
                "--max-concurrent", str(max_concurrent), "--kv-cache-fraction", str(kv_cache_fraction),
                "--block-size", str(block_size), "--scheduler", scheduler,
-               "--kv-cache-dtype", kv_cache_dtype, "--weight-dtype", weight_dtype] + ([] if cuda_graphs else ["--no-graphs"])
+               "--kv-cache-dtype", kv_cache_dtype, "--weight-dtype", weight_dtype,
+               "--weight-max-rows", str(weight_max_rows)] + ([] if cuda_graphs else ["--no-graphs"])
         console.print(f"[yellow]Tensor parallel: {tensor_parallel} ranks (RCCL)[/yellow]")
         raise typer.Exit(subprocess.call(cmd))
     server = create_inference_server(model_path=artifact, host=host, port=port, max_batch_size=max_batch_size,
                                      max_batch_tokens=max_batch_tokens, max_concurrent=max_concurrent,
                                      scheduler=scheduler, device=device, kv_cache_fraction=kv_cache_fraction,
                                      block_size=block_size, use_graphs=cuda_graphs, tensor_parallel=tensor_parallel,
-                                     kv_cache_dtype=kv_cache_dtype, weight_dtype=weight_dtype, loras=loras,
+                                     kv_cache_dtype=kv_cache_dtype, weight_dtype=weight_dtype, weight_max_rows=weight_max_rows, loras=loras,
                                      max_loras=max_loras, max_lora_rank=max_lora_rank,
                                      guide_table_words=guide_table_words)
     try:
@@ -111,5 +114,5 @@ def main(
         raise typer.Exit(1)
     start(artifact=artifact, port=port, host=host, scheduler="dynamic", max_batch_size=8, max_batch_tokens=8192,
           max_concurrent=128, device=device, kv_cache_fraction=0.85, block_size=16, cuda_graphs=True,
-          tensor_parallel=1, kv_cache_dtype="auto", weight_dtype="auto", lora=None, max_loras=0, max_lora_rank=16,
+          tensor_parallel=1, kv_cache_dtype="auto", weight_dtype="auto", weight_max_rows=16, lora=None, max_loras=0, max_lora_rank=16,
           guide_table_words=1 << 18)

@@ -75,6 +75,9 @@ class PerfKnobs:
     async_decode: bool = True      # pure decode steps pipelined: step N+1 launched (ids fed on the
                                    # device from step N's in-graph sampling) before step N's tokens are read
     tp_fused_decode: bool = True   # TP decode: all-reduce + residual + RMSNorm in one kernel
+    decode_wq_mid: bool = True     # fp8 / int4 decode weights at 17-64 token rows on the mid-batch kernel
+                                   # (decode_gemm_mid.hip); off: dequantise + bf16 path above 16 rows (A/B)
+    decode_mid_splits: int = 0     # its split-K slices (0: auto from the shape)
     moe_decode_fused: bool = True  # MoE decode MLPs on the routed-expert kernels (moe_decode.hip), in the
                                    # captured graph; off: the eager MoEMLP module per layer (A/B)
 
@@ -82,7 +85,7 @@ class PerfKnobs:
         return dataclasses.asdict(self)
 
 
-NATIVE = ("fa_split", "fa_prio", "fa_nw", "dkv", "dkv_nwg", "decode_splits", "decode_v3")
+NATIVE = ("fa_split", "fa_prio", "fa_nw", "dkv", "dkv_nwg", "decode_splits", "decode_v3", "decode_mid_splits")
 _FIELDS = {f.name: f for f in fields(PerfKnobs)}
 
 

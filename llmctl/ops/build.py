@@ -54,7 +54,9 @@ def compile_flags(arch: str, save_temps: bool = False):
 # the S / dP products AGPR destinations (occupancy-1 kernel, AGPRs free) and then moved every
 # element back with v_accvgpr_read for the softmax VALU (~120 moves per tile); the dK/dV
 # accumulators are pinned to AGPRs by their inline-asm MFMAs instead.
-FILE_FLAGS = {"flash_attn_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"]}
+# decode_gemm_mid: no packed-fp32 VALU forms (v_pk_fma_f32 and kin) in the int4 scale update.
+FILE_FLAGS = {"flash_attn_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
+              "decode_gemm_mid.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def file_flags(src: Path, flags):

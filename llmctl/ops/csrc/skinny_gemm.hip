@@ -20,19 +20,10 @@
 // 24.6 us, decode step 8.26 vs 6.87 ms; profiles/decode_gemm_nt_r5.txt).
 #include <cstdlib>
 
-#include "attn_common.h"
+#include "decode_gemm.h"
 
 namespace llmctl {
 namespace {
-
-using attn::bf16x8_t;
-using f32x4_t = __attribute__((ext_vector_type(4))) float;
-
-constexpr int KBLK = 128;  // K per block: 4 MFMA steps of 32
-
-__device__ __forceinline__ f32x4_t mfma16(bf16x8_t a, bf16x8_t b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 __device__ __forceinline__ bf16x8_t ld16(const unsigned short* p) {
   return *reinterpret_cast<const bf16x8_t*>(p);
@@ -289,16 +280,6 @@ __global__ __launch_bounds__(256) void decode_gemm_pre_kernel(const unsigned sho
 // (the f32 image's high half), and the B operand (token rows staged in LDS) follows the same k
 // order.  The row scale multiplies the fp32 partial before it is stored, so the finalize passes
 // (RoPE / SwiGLU / residual + RMSNorm) are the bf16 path's.
-__device__ __forceinline__ bf16x8_t fp8x8_to_bf16x8(unsigned lo, unsigned hi) {
-  float x[8];
-  fp8x8_to_f32(make_uint2(lo, hi), x);
-  bf16x8_t r;
-  unsigned* w = reinterpret_cast<unsigned*>(&r);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) w[j] = __builtin_amdgcn_perm(__float_as_uint(x[2 * j + 1]), __float_as_uint(x[2 * j]), 0x07060302u);
-  return r;
-}
-
 template <int NB>
 __global__ __launch_bounds__(256) void decode_gemm_w8_kernel(const unsigned short* __restrict__ x,
                                                              const unsigned char* __restrict__ w,
@@ -370,14 +351,6 @@ __global__ __launch_bounds__(256) void decode_gemm_w8_kernel(const unsigned shor
 //   * NT 16-row tiles per wave (64 NT weight rows per workgroup): the staged token rows of a chunk are
 //     as many bytes as 64 int4 weight rows, two tiles share them (and each B operand read from LDS).
 // The partials and the finalize passes are the bf16 path's.
-__device__ __forceinline__ bf16x8_t u4x8_to_bf16x8(unsigned d, unsigned mask, unsigned one28) {
-  bf16x8_t r;
-  unsigned* w = reinterpret_cast<unsigned*>(&r);
-#pragma unroll
-  for (int t = 0; t < 4; ++t) w[t] = ((d >> (4 * t)) & mask) | one28;
-  return r;
-}
-
 template <int NB, int NT>
 __global__ __launch_bounds__(256) void decode_gemm_w4_kernel(const unsigned short* __restrict__ x,
                                                              const unsigned char* __restrict__ w,
@@ -768,7 +741,7 @@ at::Tensor skinny_linear(const at::Tensor& x, const at::Tensor& w, const c10::op
 void lora_delta_into(const at::Tensor& x, const at::Tensor& idx, const at::Tensor& A, const at::Tensor& B,
                      const at::Tensor& scale, float* out, int64_t N, const char* who);
 
-// ---- fused decode projections (v2 GEMM partials + epilogue finalize), M <= 16 ------------------
+// ---- fused decode projections (GEMM partials + epilogue finalize): M <= 16, fp8 / int4 weights M <= 64 ----
 namespace {
 constexpr int kFusedKC = 1024;  // K chunk of the fused projections (config 23's)
 
@@ -781,8 +754,10 @@ void check_decode_operands(const at::Tensor& x, const at::Tensor& w, const c10::
                who, ": bf16 GPU activations, bf16, fp8 (e4m3fn) or packed int4 (uint8) weights");
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   // int4: two k per byte, w [N, K / 2]
-  LLMCTL_CHECK(w.size(1) * (w.scalar_type() == at::kByte ? 2 : 1) == K && M >= 1 && M <= 16 && N % 64 == 0 && K % KBLK == 0, who,
-               ": needs M <= 16, N % 64 == 0, K % 128 == 0 (got ", M, "x", N, "x", K, ")");
+  // fp8 / int4 weights: up to 64 rows (decode_gemm_mid.hip from 17 on)
+  const int maxM = w.scalar_type() == at::kBFloat16 ? 16 : 64;
+  LLMCTL_CHECK(w.size(1) * (w.scalar_type() == at::kByte ? 2 : 1) == K && M >= 1 && M <= maxM && N % 64 == 0 && K % KBLK == 0, who,
+               ": needs M <= ", maxM, ", N % 64 == 0, K % 128 == 0 (got ", M, "x", N, "x", K, ")");
   if (bias.has_value() && bias->defined())
     LLMCTL_CHECK(bias->scalar_type() == at::kBFloat16 && bias->is_contiguous() && bias->numel() == N, who,
                  ": bias [N] bf16");
@@ -802,7 +777,8 @@ int decode_partials(const at::Tensor& x, const at::Tensor& w, at::Tensor& ws,
                     const c10::optional<at::Tensor>& w_scale = c10::nullopt, int extra = 0) {
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   const int KC = std::min(kFusedKC, K);
-  const int KS = (K + KC - 1) / KC;
+  const bool mid = M > 16;  // fp8 / int4 only (check_decode_operands): the mid-batch kernel, its own slice count
+  const int KS = mid ? decode_mid_splits(M, N, K, w_int4(w)) : (K + KC - 1) / KC;
   ws = at::empty({(long)(KS + extra) * M * N}, x.options().dtype(at::kFloat));
   if (w_fp8(w)) {
     // (two 16-row tiles per wave, and K chunks of 512 / 2048, measured 3-6 % slower in the decode
@@ -810,6 +786,10 @@ int decode_partials(const at::Tensor& x, const at::Tensor& w, at::Tensor& ws,
     LLMCTL_CHECK(w_scale.has_value() && w_scale->defined() && w_scale->scalar_type() == at::kFloat &&
                      w_scale->is_contiguous() && w_scale->numel() == N && w_scale->is_cuda(),
                  "fp8 decode weights need fp32 row scales [N] on the GPU");
+    if (mid) {
+      launch_decode_mid(x, w, *w_scale, ws.data_ptr<float>(), KS);
+      return KS;
+    }
     hipLaunchKernelGGL((decode_gemm_w8_kernel<kFusedKC / KBLK>), dim3(N / 64, KS), dim3(256),
                        (size_t)16 * (kFusedKC + 8) * 2, stream(), bf_ptr(x),
                        static_cast<const unsigned char*>(w.data_ptr()), w_scale->data_ptr<float>(),
@@ -819,6 +799,10 @@ int decode_partials(const at::Tensor& x, const at::Tensor& w, at::Tensor& ws,
                      w_scale->is_contiguous() && w_scale->dim() == 2 && w_scale->size(0) == N &&
                      w_scale->size(1) == K / KBLK && w_scale->is_cuda(),
                  "int4 decode weights need fp32 group scales [N, K / 128] on the GPU");
+    if (mid) {
+      launch_decode_mid(x, w, *w_scale, ws.data_ptr<float>(), KS);
+      return KS;
+    }
     const unsigned char* wp = w.data_ptr<unsigned char>();
     // one 16-row tile per wave, or two (128 weight rows per workgroup share the staged token rows, which
     // are as many bytes as 64 int4 rows) on the wide projections: at 16 tokens two tiles measured 23.6 vs

@@ -510,7 +510,7 @@ def _dequant(w, w_scale, dtype):
 def decode_linear_fp8(x, w, w_scale, b=None, lora: Optional[LoRARows] = None):
     """``x @ (w * w_scale[:, None])^T (+ b)`` for decode-shaped inputs with fp8 (OCP e4m3fn)
     weights and fp32 row scales (W8A16: ``csrc/skinny_gemm.hip``'s fp8 weight stream, half the
-    bytes of the bf16 one)."""
+    bytes of the bf16 one; ``csrc/decode_gemm_mid.hip`` at 17-64 tokens)."""
     if decode_fused_ok(x, w):
         return native().decode_linear_fp8(x, w, w_scale, b, *_lora_args(lora))
     return decode_linear(x, _dequant(w, w_scale, x.dtype), b, lora)
@@ -519,7 +519,8 @@ def decode_linear_fp8(x, w, w_scale, b=None, lora: Optional[LoRARows] = None):
 def decode_linear_int4(x, qweight, scale, b=None, lora: Optional[LoRARows] = None):
     """``x @ dequant(qweight, scale)^T (+ b)`` for decode-shaped inputs with group-128 int4 weights
     (W4A16, ``quantizers.quantize_int4_g128``: uint8 ``[N, K/2]`` + fp32 scales ``[N, K/128]``;
-    ``csrc/skinny_gemm.hip``'s int4 weight stream, 4.25 bits per weight)."""
+    ``csrc/skinny_gemm.hip``'s int4 weight stream, 4.25 bits per weight;
+    ``csrc/decode_gemm_mid.hip`` at 17-64 tokens)."""
     if decode_fused_ok(x, qweight):
         return native().decode_linear_int4(x, qweight, scale, b, *_lora_args(lora))
     return decode_linear(x, _dequant(qweight, scale, x.dtype), b, lora)
@@ -528,11 +529,14 @@ def decode_linear_int4(x, qweight, scale, b=None, lora: Optional[LoRARows] = Non
 def decode_fused_ok(x, w) -> bool:
     """Can this decode projection run with a fused epilogue (``csrc/skinny_gemm.hip``: the v2
     weight-streaming GEMM's K-chunk partials summed by a finalize pass that also applies RoPE +
-    paged-cache write, SwiGLU or residual + RMSNorm)?  <= 16 tokens, bf16 activations, bf16 / fp8
-    (e4m3fn) / packed int4 (uint8 ``[N, K/2]``) weights, out features a multiple of 64, in features
-    of 128.  Knob ``decode_fused`` off disables (A/B)."""
-    return (knobs().decode_fused and use_native(x) and x.dim() == 2
-            and 1 <= x.shape[0] <= 16 and x.dtype == torch.bfloat16
+    paged-cache write, SwiGLU or residual + RMSNorm)?  <= 16 tokens -- <= 64 with fp8 / int4 weights
+    (``csrc/decode_gemm_mid.hip`` from 17 on; knob ``decode_wq_mid`` off keeps 16) --, bf16
+    activations, bf16 / fp8 (e4m3fn) / packed int4 (uint8 ``[N, K/2]``) weights, out features a
+    multiple of 64, in features of 128.  Knob ``decode_fused`` off disables (A/B)."""
+    k = knobs()
+    max_rows = 64 if w.dtype in (torch.float8_e4m3fn, torch.uint8) and k.decode_wq_mid else 16
+    return (k.decode_fused and use_native(x) and x.dim() == 2
+            and 1 <= x.shape[0] <= max_rows and x.dtype == torch.bfloat16
             and w.dtype in (torch.bfloat16, torch.float8_e4m3fn, torch.uint8) and x.is_contiguous()
             and w.is_contiguous() and w.shape[0] % 64 == 0 and x.shape[1] % 128 == 0)
 

@@ -60,7 +60,7 @@ class InferenceEngine:
                  use_graphs: bool = True, seed: int = 0, pc=None, prefix_caching: bool = True,
                  tuning_cache: Optional[str] = None, perf_knobs: Optional[Dict] = None,
                  kv_cache_dtype: str = "auto", weight_dtype: str = "auto", max_loras: int = 0,
-                 max_lora_rank: int = 16, guide_table_words: int = 1 << 18):
+                 max_lora_rank: int = 16, guide_table_words: int = 1 << 18, weight_max_rows: int = 16):
         from llmctl.config import knobs as perf
 
         self.knobs = perf.configure(perf_knobs)  # defaults + perf_knobs + LLMCTL_KNOBS
@@ -105,6 +105,13 @@ class InferenceEngine:
             self._wq_kind = "int4"
         elif weight_dtype not in ("auto", "model", "bf16", "bfloat16"):
             raise ValueError(f"weight_dtype must be auto / bf16 / fp8 / int4, got {weight_dtype!r}")
+        # most token rows of a decode step that stream the quantised copies: 16 (the <= 16-row kernels),
+        # or 32 / 64 (csrc/decode_gemm_mid.hip from 17 rows on); larger steps stream the bf16 weights
+        if weight_max_rows not in (16, 32, 64):
+            raise ValueError(f"weight_max_rows must be 16, 32 or 64, got {weight_max_rows!r}")
+        if self._wq_kind is None and weight_max_rows != self.W8_MAX_ROWS:
+            log.info("engine: weight_max_rows=%d ignored (weight_dtype is auto)", weight_max_rows)
+        self.weight_max_rows = int(weight_max_rows)
         if self._wq_kind is not None and self.device.type == "cuda":
             self._wq = self._quantize_decode_weights(self._wq_kind)
         self.weight_dtype = self._wq_kind if self._wq is not None else "auto"
@@ -736,13 +743,13 @@ class InferenceEngine:
                  len(pairs), nbytes / 1e9)
         return out
 
-    W8_MAX_ROWS = 16  # the fused fp8 / int4 decode kernels take at most 16 token rows (ops.decode_fused_ok)
+    W8_MAX_ROWS = 16  # default of ``weight_max_rows``: the fp8 / int4 copies serve steps of up to 16 token rows
 
     def _dw(self, li: int, layer, name: str, n: int):
         """(weight, scales or None) the fused decode path streams for ``layer.name`` at ``n`` token
         rows: the fp8 / int4 copy only where the fused kernel takes it, else the bf16 weight (which
         is kept) -- never a per-step dequantised fp32 image of the copy."""
-        if self._wq is not None and 1 <= n <= self.W8_MAX_ROWS and name in self._wq[li]:
+        if self._wq is not None and 1 <= n <= self.weight_max_rows and name in self._wq[li]:
             q = self._wq[li][name]
             if name not in ("wo", "w_down") or q[0].shape[0] <= 16384:  # add+RMSNorm finalize limit
                 return q
@@ -790,7 +797,7 @@ class InferenceEngine:
             else:
                 xn, res = ops.decode_linear_add_rmsnorm(act, wd, layer.b_down, res, nw, eps, w_scale=sd,
                                                         lora=rows(li, "w_down"))
-        if self._wq_head is not None and n <= self.W8_MAX_ROWS:
+        if self._wq_head is not None and n <= self.weight_max_rows:
             return self._gather_vocab(lin(xn, *self._wq_head))
         return self._gather_vocab(ops.decode_linear(xn, m.head_weight()))
 

@@ -282,6 +282,8 @@ def main(argv=None) -> int:
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--kv-cache-dtype", default="auto")
     ap.add_argument("--weight-dtype", default="auto", help="auto | fp8 | int4 (decode projection weights)")
+    ap.add_argument("--weight-max-rows", type=int, default=16,
+                    help="16 | 32 | 64: most decode rows that stream the fp8 / int4 copies")
     ap.add_argument("--control-timeout", type=float, default=600.0,
                     help="seconds a frozen TP peer may stop heart-beating before the others exit")
     a = ap.parse_args(argv)
@@ -290,7 +292,7 @@ def main(argv=None) -> int:
                             max_batch_tokens=a.max_batch_tokens, kv_cache_fraction=a.kv_cache_fraction,
                             block_size=a.block_size, scheduler=a.scheduler, use_graphs=not a.no_graphs,
                             kv_cache_dtype=a.kv_cache_dtype, weight_dtype=a.weight_dtype,
-                            control_timeout_s=a.control_timeout)
+                            weight_max_rows=a.weight_max_rows, control_timeout_s=a.control_timeout)
     from .control import PeerLostError
 
     if eng.tp_rank != 0:
