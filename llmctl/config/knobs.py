@@ -80,6 +80,8 @@ class PerfKnobs:
     decode_mid_splits: int = 0     # its split-K slices (0: auto from the shape)
     moe_decode_fused: bool = True  # MoE decode MLPs on the routed-expert kernels (moe_decode.hip), in the
                                    # captured graph; off: the eager MoEMLP module per layer (A/B)
+    moe_decode_wq: bool = True     # expert_weight_dtype=fp8 / int4: the routed MLPs stream the quantised experts
+                                   # (moe_decode_wq.hip); off: the bf16 experts on the routed kernels (A/B)
 
     def as_dict(self) -> Dict[str, Any]:
         return dataclasses.asdict(self)

@@ -30,6 +30,7 @@ from .functional import (
     lora_delta,
     LoRARows,
     MoEExpertTable,
+    MoEQuantExperts,
     moe_decode_down_add_rmsnorm,
     moe_decode_ok,
     moe_decode_up_swiglu,
@@ -62,5 +63,5 @@ __all__ = [
     "paged_prefill_attention", "prefill_work_list", "attn_merge_",
     "rmsnorm", "rope_qkv", "rope_flash_attention", "rope_qkv_cache", "sample", "sample_ext", "sample_guided", "guide_state_reset", "sampler_state_reset", "swiglu", "transpose_", "up_swiglu",
     "prompt_logprobs", "rms_rstd", "linear_rowscale", "up_swiglu_rowscale", "linear_acc_",
-    "LoRARows", "lora_delta", "MoEExpertTable", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",
+    "LoRARows", "lora_delta", "MoEExpertTable", "MoEQuantExperts", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",
 ]

@@ -690,6 +690,38 @@ class MoEExpertTable:
         return self.ptrs.tolist() != [t.data_ptr() for t in self.tensors]
 
 
+class MoEQuantExperts:
+    """One projection's expert weights quantised for ``csrc/moe_decode_wq.hip``: every expert through
+    the project's quantizer -- ``kind`` ``"fp8"`` (``quantizers.quantize_fp8``: e4m3fn, one fp32 scale
+    per output row) or ``"int4"`` (``quantizers.quantize_int4_g128``: offset-binary nibbles, fp32
+    scales per row and group of 128 input features) -- and stacked: ``qweight`` ``[E, N, K]`` fp8 or
+    ``[E, N, K/2]`` uint8, ``scale`` ``[E, N]`` or ``[E, N, K/128]``.  ``shape`` is an expert's ``(N, K)``."""
+
+    def __init__(self, experts, kind: str):
+        from llmctl.plugins.quantizers import quantize_fp8, quantize_int4_g128
+
+        if kind not in ("fp8", "int4"):
+            raise ValueError(f"MoEQuantExperts: kind must be fp8 or int4, got {kind!r}")
+        experts = [e.detach() for e in experts]
+        if not experts:
+            raise ValueError("MoEQuantExperts: no experts")
+        t0 = experts[0]
+        if any(t.dim() != 2 or t.shape != t0.shape or t.device != t0.device for t in experts):
+            raise ValueError("MoEQuantExperts: the experts must be 2-D tensors of one shape on one device")
+        qd = [(quantize_fp8 if kind == "fp8" else quantize_int4_g128)(t) for t in experts]
+        self.kind, self.E, self.shape, self.device = kind, len(experts), tuple(t0.shape), t0.device
+        self.qweight = torch.stack([d["qweight"] for d in qd]).contiguous()
+        self.scale = torch.stack([d["scale"].float() for d in qd]).contiguous()
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.qweight, self.scale))
+
+    def dequantized(self):
+        """The fp32 experts the quantised stack stands for (``ref.moe_dequant_experts``)."""
+        return ref.moe_dequant_experts(self.qweight, self.scale)
+
+
 def moe_decode_ok(x, E: int, k: int, h: int, F: int) -> bool:
     """Can a decode step's routed MLP run on the ``csrc/moe_decode.hip`` kernels?  1..64 bf16 token
     rows on the GPU, <= 64 experts, 1 <= k <= min(E, 8), hidden and expert width multiples of 128,
@@ -703,6 +735,12 @@ def _moe_table_ok(x, table: MoEExpertTable) -> bool:
     return table.dtype == torch.bfloat16 and table.device == x.device
 
 
+def _moe_wq_ok(x, q: MoEQuantExperts) -> bool:
+    """The quantised routed kernel's own limits: the stack on ``x``'s device, out features a multiple
+    of 64 (fp8) or 128 (int4: two 16-row tiles per wave)."""
+    return q.device == x.device and q.shape[0] % (128 if q.kind == "int4" else 64) == 0 and q.shape[1] % 128 == 0
+
+
 def moe_route(x, w_router, k: int):
     """``(topi int32 [M, k], topw fp32 [M, k])``: softmax (fp32) of the router logits
     ``linear(x, w_router)`` (rounded to the activation dtype), the k most probable experts per
@@ -713,18 +751,30 @@ def moe_route(x, w_router, k: int):
     return ref.moe_route(x, w_router, k)
 
 
-def moe_decode_up_swiglu(x, up: MoEExpertTable, topi):
+def moe_decode_up_swiglu(x, up, topi):
     """``act [M k, F]``: row ``t k + j`` is ``silu(g) * u`` of ``x[t] @ W_up[topi[t, j]]^T``
-    (``W_up[e] = [2F, h]``, gate rows first).  Unrouted experts' weights are not read."""
+    (``W_up[e] = [2F, h]``, gate rows first).  Unrouted experts' weights are not read.  ``up``: a
+    ``MoEExpertTable`` (bf16 experts) or a ``MoEQuantExperts`` (fp8 / int4: ``csrc/moe_decode_wq.hip``)."""
     F_ = up.shape[0] // 2
+    if isinstance(up, MoEQuantExperts):  # quantised experts: the kernel, else the oracle on their dequantised image
+        if moe_decode_ok(x, up.E, topi.shape[1], up.shape[1], F_) and _moe_wq_ok(x, up):
+            return native().moe_decode_up_swiglu_wq(x, up.qweight, up.scale, topi)
+        return ref.moe_decode_up_swiglu(x, up.dequantized(), topi).to(x.dtype)
     if moe_decode_ok(x, up.E, topi.shape[1], up.shape[1], F_) and _moe_table_ok(x, up):
         return native().moe_decode_up_swiglu(x, up.ptrs, topi, up.E, F_)
     return ref.moe_decode_up_swiglu(x, up.tensors, topi).to(x.dtype)
 
 
-def moe_decode_down_add_rmsnorm(act, down: MoEExpertTable, topi, topw, residual, norm_w, eps: float):
+def moe_decode_down_add_rmsnorm(act, down, topi, topw, residual, norm_w, eps: float):
     """``(rmsnorm(s) * norm_w, s)`` with ``s = sum_j topw[t, j] (act[t k + j] @ W_down[topi[t, j]]^T)
-    + residual`` (``W_down[e] = [h, F]``; fixed-order combine in slot order, no atomics)."""
+    + residual`` (``W_down[e] = [h, F]``; fixed-order combine in slot order, no atomics).  ``down``: a
+    ``MoEExpertTable`` or a ``MoEQuantExperts``."""
+    if isinstance(down, MoEQuantExperts):
+        if moe_decode_ok(residual, down.E, topi.shape[1], down.shape[0], down.shape[1]) and _moe_wq_ok(act, down):
+            return native().moe_decode_down_add_rmsnorm_wq(act, down.qweight, down.scale, topi, topw, residual, norm_w,
+                                                           eps)
+        xn, s = ref.moe_decode_down_add_rmsnorm(act, down.dequantized(), topi, topw, residual, norm_w, eps)
+        return xn.to(residual.dtype), s.to(residual.dtype)
     if moe_decode_ok(residual, down.E, topi.shape[1], down.shape[0], down.shape[1]) and _moe_table_ok(act, down):
         return native().moe_decode_down_add_rmsnorm(act, down.ptrs, topi, topw, residual, norm_w, eps, down.E)
     xn, s = ref.moe_decode_down_add_rmsnorm(act, down.tensors, topi, topw, residual, norm_w, eps)
@@ -818,5 +868,5 @@ __all__ = [
     "sample", "sample_ext", "sample_guided", "prompt_logprobs", "guide_state_reset", "sampler_state_reset", "decode_linear", "decode_linear_fp8", "decode_linear_int4", "decode_fused_ok", "decode_qkv_rope_cache", "decode_up_swiglu", "decode_attention_qkv", "up_swiglu",
     "decode_linear_add_rmsnorm", "rope_qkv_cache", "paged_prefill_attention", "prefill_work_list", "attn_merge_",
     "rms_rstd", "rowscale_ok", "linear_rowscale", "up_swiglu_rowscale", "linear_acc_",
-    "MoEExpertTable", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",
+    "MoEExpertTable", "MoEQuantExperts", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",
 ]

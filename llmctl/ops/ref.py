@@ -662,6 +662,15 @@ def moe_decode_down_add_rmsnorm(act, experts_down, topi, topw, residual, norm_w,
     return xn, s
 
 
+def moe_dequant_experts(qweight: torch.Tensor, scale: torch.Tensor):
+    """The fp32 experts of a quantised stack (``ops.MoEQuantExperts``): ``qweight`` uint8
+    ``[E, N, K/2]`` with group scales ``[E, N, K/128]`` (int4, :func:`dequant_int4_g128`), or fp8
+    ``[E, N, K]`` with row scales ``[E, N]``."""
+    if qweight.dtype == torch.uint8:
+        return [dequant_int4_g128(q, s) for q, s in zip(qweight, scale)]
+    return [q.float() * s.float().unsqueeze(1) for q, s in zip(qweight, scale)]
+
+
 def moe_decode_mlp(x, experts_up, experts_down, topi, topw, residual, norm_w, eps: float):
     """The whole routed MLP of a decode step in fp32 with no intermediate rounding: expert SwiGLU
     MLPs of the routed copies, weighted combine, residual add and RMSNorm -> ``(xn, res_out)``."""

@@ -60,7 +60,8 @@ class InferenceEngine:
                  use_graphs: bool = True, seed: int = 0, pc=None, prefix_caching: bool = True,
                  tuning_cache: Optional[str] = None, perf_knobs: Optional[Dict] = None,
                  kv_cache_dtype: str = "auto", weight_dtype: str = "auto", max_loras: int = 0,
-                 max_lora_rank: int = 16, guide_table_words: int = 1 << 18, weight_max_rows: int = 16):
+                 max_lora_rank: int = 16, guide_table_words: int = 1 << 18, weight_max_rows: int = 16,
+                 expert_weight_dtype: str = "auto"):
         from llmctl.config import knobs as perf
 
         self.knobs = perf.configure(perf_knobs)  # defaults + perf_knobs + LLMCTL_KNOBS
@@ -115,6 +116,19 @@ class InferenceEngine:
         if self._wq_kind is not None and self.device.type == "cuda":
             self._wq = self._quantize_decode_weights(self._wq_kind)
         self.weight_dtype = self._wq_kind if self._wq is not None else "auto"
+        # routed-expert weights of an MoE model on the decode path: the model's ("auto"), or fp8 / int4
+        # copies (the formats above, stacked per layer: ops.MoEQuantExperts) that the routed-expert
+        # kernels stream instead (csrc/moe_decode_wq.hip).  Independent of weight_dtype, which governs
+        # the attention projections and the LM head.  Prefill and steps above MOE_MAX_ROWS rows keep
+        # the bf16 experts.  Made before the KV cache is sized.
+        self._moe_q: Optional[List[Tuple[ops.MoEQuantExperts, ops.MoEQuantExperts]]] = None
+        if expert_weight_dtype in ("fp8", "fp8_e4m3", "float8_e4m3fn"):
+            self._moe_q = self._quantize_experts("fp8")
+        elif expert_weight_dtype in ("int4", "int4-g128", "w4a16"):
+            self._moe_q = self._quantize_experts("int4")
+        elif expert_weight_dtype not in ("auto", "model", "bf16", "bfloat16"):
+            raise ValueError(f"expert_weight_dtype must be auto / bf16 / fp8 / int4, got {expert_weight_dtype!r}")
+        self.expert_weight_dtype = self._moe_q[0][0].kind if self._moe_q is not None else "auto"
         # prefill with the RMSNorms folded into the QKV / gate-up projections (knob
         # prefill_norm_fold): copies of those weights with the norm weight multiplied into their K
         # columns ((H + 2 kv) D + 2 F) H bf16 per layer, made before the KV cache is sized
@@ -160,9 +174,9 @@ class InferenceEngine:
         # MoE decode on the routed-expert kernels (ops.moe_route / moe_decode_up_swiglu /
         # moe_decode_down_add_rmsnorm): per layer, the pointer tables of the expert weights
         self._moe: Optional[List[Tuple[ops.MoEExpertTable, ops.MoEExpertTable]]] = self._moe_tables()
-        if self._moe is not None and self._wq is not None:
-            log.info("engine: %s decode weights cover the attention projections; the experts stay bf16",
-                     self.weight_dtype)
+        if self._moe is not None and self._wq is not None and self._moe_q is None:
+            log.info("engine: %s decode weights cover the attention projections; the experts stay bf16 "
+                     "(expert_weight_dtype quantises them)", self.weight_dtype)
         # the eager MoE module sizes the expert segments on the host: graphs only on the routed kernels
         self.use_graphs = use_graphs and self.device.type == "cuda" and (not cfg.is_moe or self._fused_decode())
         self._graphs: Dict[int, Tuple[torch.cuda.CUDAGraph, Dict[str, torch.Tensor]]] = {}
@@ -246,6 +260,21 @@ class InferenceEngine:
                     or up.shape != (2 * cfg.moe_ffn, cfg.hidden) or down.shape != (cfg.hidden, cfg.moe_ffn)):
                 return None
             out.append((up, down))
+        return out
+
+    @torch.no_grad()
+    def _quantize_experts(self, kind: str):
+        """(up, down) ``ops.MoEQuantExperts`` per layer for ``expert_weight_dtype``, or None (with a log
+        line) where the routed-expert kernels do not serve the model: a dense model, the CPU, TP or
+        EP > 1, a dtype other than bf16 (``_moe_tables``)."""
+        if not self.cfg.is_moe or self._moe_tables() is None:
+            log.info("engine: expert_weight_dtype=%s ignored (%s)", kind, "a dense model" if not self.cfg.is_moe
+                     else "the routed-expert decode kernels do not serve this model here")
+            return None
+        out = [(ops.MoEQuantExperts(layer.moe.experts_up, kind), ops.MoEQuantExperts(layer.moe.experts_down, kind))
+               for layer in self.model.layers]
+        log.info("engine: %s expert weight copies of %d MoE layers: %.3f GB (out of the KV cache budget)", kind,
+                 len(out), sum(q.nbytes for pair in out for q in pair) / 1e9)
         return out
 
     def _moe_fused(self, n: int = 1) -> bool:
@@ -786,7 +815,8 @@ class InferenceEngine:
                                                         layer.mlp_norm_w, eps, w_scale=so, lora=rows(li, "wo"))
             nw = layers[li + 1].attn_norm_w if li + 1 < len(layers) else m.final_norm_w
             if layer.moe is not None:  # routed experts: all routing stays on the device
-                up_t, down_t = self._moe[li]
+                # (expert_weight_dtype: the fp8 / int4 copies; knob moe_decode_wq off: the bf16 experts, A/B)
+                up_t, down_t = self._moe_q[li] if self._moe_q is not None and self.knobs.moe_decode_wq else self._moe[li]
                 topi, topw = ops.moe_route(xn, layer.moe.w_router, layer.moe.k)
                 act = ops.moe_decode_up_swiglu(xn, up_t, topi)
                 xn, res = ops.moe_decode_down_add_rmsnorm(act, down_t, topi, topw, res, nw, eps)
@@ -957,7 +987,7 @@ class InferenceEngine:
         self._lora = None
         self._lora_slots, self._lora_salt, self._lora_scale = {}, {}, {}
         self._nf = None
-        self._moe = None
+        self._moe = self._moe_q = None
         self.rope = None
         if self.device.type == "cuda":
             torch.cuda.empty_cache()

@@ -13,6 +13,14 @@ step, as a slope) and the expert bytes a step must move (from the routing of one
 distinct experts picked per layer x 3 h F x 2 B) next to the bytes of all experts.
 
     python tools/moe_decode_bench.py [--steps 200] [--warmup 3] [--reps 5] [--ctx 2048]
+
+``--expert-weight-dtype fp8,int4`` measures instead the routed path over bf16 experts against the same
+path over fp8 / int4 experts (``InferenceEngine(expert_weight_dtype=...)``, csrc/moe_decode_wq.hip):
+same slices, batches and alternation, plus the expert bytes a step moves per layer in each format
+and those bytes over the per-layer time.  ``--expert-weight-dtype bf16`` times the bf16 experts alone
+(to compare two commits' default path in alternated runs).
+
+    python tools/moe_decode_bench.py --expert-weight-dtype fp8,int4 [--steps 200] [--reps 5]
 """
 import argparse
 import dataclasses
@@ -48,12 +56,12 @@ class SliceEngine(InferenceEngine):
         return model, cfg, None
 
 
-def make_engine(L, ctx, fused):
+def make_engine(L, ctx, fused, **kw):
     cls = type(f"SliceEngine{L}", (SliceEngine,), {"SLICE_LAYERS": L})
     max_len = ctx + 64
     return cls("mixtral-8x7b", device="cuda", max_batch_size=max(BATCHES), max_model_len=max_len,
                num_kv_blocks=max(BATCHES) * ((max_len + 15) // 16) + 64, block_size=16, prefix_caching=False,
-               perf_knobs={"moe_decode_fused": int(fused)})
+               perf_knobs={"moe_decode_fused": int(fused)}, **kw)
 
 
 def prefill(eng, ctx):
@@ -135,14 +143,70 @@ def routed_experts(eng, plan):
     return [int(t.unique().numel()) for t in picked]
 
 
+def expert_nbytes(mode, h, F):
+    """Bytes of one expert (gate/up + down) as the routed kernels stream it, scales included."""
+    if mode == "fp8":
+        return 3 * h * F + (2 * F + h) * 4
+    if mode == "int4":
+        return 3 * h * F // 2 + 3 * h * F // 128 * 4
+    return 3 * h * F * 2
+
+
+def main_wq(a, cfg):
+    """bf16 experts against fp8 / int4 experts, all on the routed kernels in captured graphs."""
+    h, F, E, k = cfg.hidden, cfg.moe_ffn, cfg.num_experts, cfg.experts_per_token
+    modes = ["bf16"] + [m for m in a.expert_weight_dtype.split(",") if m and m != "bf16"]
+    print(f"# MoE decode, expert weight formats {modes}: mixtral-8x7b dimensions (hidden {h}, {E} experts x ffn {F}, "
+          f"top-{k}), context {a.ctx}, {torch.cuda.get_device_name(0)}")
+    print(f"# ms per decode step: median (min-max) of {a.reps} x {a.steps} steps after {a.warmup} warm-up steps, "
+          f"modes alternated; routed-expert kernels in the captured graph in every mode")
+    ms, routed = {}, {}
+    for L in (2, 4):
+        engs = {m: make_engine(L, a.ctx, True, **({} if m == "bf16" else {"expert_weight_dtype": m})) for m in modes}
+        assert all(e.use_graphs and (m == "bf16" or e.expert_weight_dtype == m) for m, e in engs.items())
+        seqs = {m: prefill(e, a.ctx) for m, e in engs.items()}
+        for B in BATCHES:
+            plans = {m: engs[m].decode_plan(seqs[m][:B]) for m in modes}
+            t = {m: [] for m in modes}
+            for _ in range(a.reps):
+                for m in modes:
+                    t[m].append(time_steps(engs[m], plans[m], a.steps, a.warmup))
+            for m in modes:
+                ms[(L, B, m)] = statistics.median(t[m])
+            routed[(L, B)] = routed_experts(engs["bf16"], plans["bf16"])
+            print(f"layers {L} batch {B:2d}: " + "  ".join(f"{m} {ms[(L, B, m)]:7.3f} ms/step ({min(t[m]):.3f}-{max(t[m]):.3f})"
+                                                          for m in modes) + f"  (distinct experts per layer {routed[(L, B)]})")
+        for e in engs.values():
+            e.close()
+        del engs, seqs
+        _MODELS.clear()
+        torch.cuda.empty_cache()
+    print("#")
+    print("# per layer (slope between the 4- and the 2-layer slice); expert MB = distinct routed experts (bf16 run, mean "
+          "over the 4 layers) x one expert's bytes in the format; TB/s = those bytes over the whole layer's time "
+          "(attention included: a lower bound of the routed kernels' rate)")
+    print("# batch | format | ms/layer | vs bf16 | expert MB/layer | TB/s")
+    for B in BATCHES:
+        base = (ms[(4, B, "bf16")] - ms[(2, B, "bf16")]) / 2
+        for m in modes:
+            per = (ms[(4, B, m)] - ms[(2, B, m)]) / 2
+            mb = statistics.mean(routed[(4, B)]) * expert_nbytes(m, h, F) / 1e6
+            print(f"{B:7d} | {m:>6} | {per:8.3f} | {base / per:6.2f}x | {mb:15.0f} | {mb / 1e6 / (per / 1e3):5.2f}"
+                  + ("" if per <= base else "  (NOT faster)"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--ctx", type=int, default=2048)
+    ap.add_argument("--expert-weight-dtype", default=None,
+                    help="comma list of fp8, int4 (or bf16 alone): time these expert formats against bf16 experts")
     a = ap.parse_args()
     cfg = get_model_config("mixtral-8x7b")
+    if a.expert_weight_dtype:
+        return main_wq(a, cfg)
     h, F, E, k = cfg.hidden, cfg.moe_ffn, cfg.num_experts, cfg.experts_per_token
     expert_bytes = 3 * h * F * 2
     print(f"# MoE decode A/B: mixtral-8x7b dimensions (hidden {h}, {E} experts x ffn {F}, top-{k}, GQA "
