@@ -22,7 +22,7 @@ def run_serving_benchmark(model: str = "gpt-7b", prompt_length: int = 2048, gen_
                           kv_cache_dtype: str = "auto", weight_dtype: str = "auto",
                           sampling: Optional[Dict[str, Any]] = None, num_loras: int = 0,
                           lora_rank: int = 16, weight_max_rows: int = 16,
-                          expert_weight_dtype: str = "auto") -> Dict[str, Any]:
+                          expert_weight_dtype: str = "auto", moe_max_rows: int = 64) -> Dict[str, Any]:
     """``sampling``: extra ``SamplingParams`` fields of every request (penalties, logprobs), to
     time the extended sampler end to end (or ``guided_regex``: the guided sampler; such requests
     end with EOS; or ``prompt_logprobs``: every prompt is scored in its prefill, which TTFT then
@@ -41,7 +41,8 @@ def run_serving_benchmark(model: str = "gpt-7b", prompt_length: int = 2048, gen_
                           max_model_len=max_len,
                           use_graphs=use_graphs, seed=seed, scheduler=scheduler, kv_cache_dtype=kv_cache_dtype,
                           weight_dtype=weight_dtype, weight_max_rows=weight_max_rows, max_loras=num_loras,
-                          max_lora_rank=lora_rank, expert_weight_dtype=expert_weight_dtype)
+                          max_lora_rank=lora_rank, expert_weight_dtype=expert_weight_dtype,
+                          moe_max_rows=moe_max_rows)
     names = []
     if num_loras > 0:
         from llmctl.serve.lora import random_adapter
@@ -98,6 +99,7 @@ def run_serving_benchmark(model: str = "gpt-7b", prompt_length: int = 2048, gen_
         "prompt_length": prompt_length, "gen_length": gen_length, "qps": qps, "max_batch_size": max_batch_size, "scheduler": scheduler,
         "kv_cache_dtype": str(eng.kv_dtype).replace("torch.", ""), "decode_weight_dtype": eng.weight_dtype,
         "expert_weight_dtype": eng.expert_weight_dtype,
+        "moe_max_rows": eng.moe_max_rows,
         "max_batch_tokens": eng.scheduler.max_batch_tokens,
         "ttft_p50_ms": round(float(np.percentile(ttft, 50)) * 1e3, 2),
         "ttft_p90_ms": round(float(np.percentile(ttft, 90)) * 1e3, 2),

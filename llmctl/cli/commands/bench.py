@@ -54,6 +54,7 @@ def e2e(
     weight_dtype: str = typer.Option("auto", help="Decode projection weights: auto (model dtype) | fp8 (e4m3fn, row scales) | int4 (group-128 scales)"),
     weight_max_rows: int = typer.Option(16, help="Most decode rows that stream the fp8 / int4 copies: 16 | 32 | 64"),
     expert_weight_dtype: str = typer.Option("auto", help="MoE routed-expert decode weights: auto (model dtype) | fp8 | int4"),
+    moe_max_rows: int = typer.Option(64, help="Most rows of a step whose MoE MLPs run on HIP kernels: 64 .. 8192"),
     presence_penalty: float = typer.Option(0.0, help="Presence penalty of every request (extended sampler)"),
     frequency_penalty: float = typer.Option(0.0, help="Frequency penalty of every request (extended sampler)"),
     repetition_penalty: float = typer.Option(1.0, help="Repetition penalty of every request (extended sampler)"),
@@ -77,7 +78,7 @@ def e2e(
                                 num_requests=num_requests, max_batch_size=max_batch_size, device=device,
                                 scheduler=scheduler, max_batch_tokens=max_batch_tokens, kv_cache_dtype=kv_cache_dtype,
                                 weight_dtype=weight_dtype, weight_max_rows=weight_max_rows, num_loras=num_loras, lora_rank=lora_rank,
-                                expert_weight_dtype=expert_weight_dtype,
+                                expert_weight_dtype=expert_weight_dtype, moe_max_rows=moe_max_rows,
                                 sampling={"presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty,
                                           "repetition_penalty": repetition_penalty, "logprobs": logprobs,
                                           "guided_regex": guided_regex, "prompt_logprobs": prompt_logprobs})

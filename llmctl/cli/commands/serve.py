@@ -41,6 +41,9 @@ def start(
     expert_weight_dtype: str = typer.Option("auto", help="Routed-expert weights of an MoE model on the decode path: "
                                                          "auto (the model dtype), fp8 or int4 (the --weight-dtype "
                                                          "formats; independent of it)"),
+    moe_max_rows: int = typer.Option(64, help="Most token rows of a step whose MoE MLPs run on HIP kernels: 64 (decode "
+                                              "steps only) or up to 8192 (prefill chunks, mixed steps and larger "
+                                              "decode steps on the grouped-expert kernels)"),
     lora: Optional[List[str]] = typer.Option(None, "--lora", help="NAME=PATH of a LoRA adapter directory to serve "
                                                                    "under NAME (repeatable)"),
     max_loras: int = typer.Option(0, help="Resident LoRA adapter slots (at least the number of --lora)"),
@@ -89,6 +92,8 @@ def start(
         console.print(f"[yellow]Tensor parallel: {tensor_parallel} ranks (RCCL)[/yellow]")
         if expert_weight_dtype != "auto":
             console.print("[yellow]--expert-weight-dtype ignored: the experts stay bf16 at TP > 1[/yellow]")
+        if moe_max_rows != 64:
+            console.print("[yellow]--moe-max-rows ignored: the routed-expert kernels serve TP = 1[/yellow]")
         raise typer.Exit(subprocess.call(cmd))
     server = create_inference_server(model_path=artifact, host=host, port=port, max_batch_size=max_batch_size,
                                      max_batch_tokens=max_batch_tokens, max_concurrent=max_concurrent,
@@ -96,7 +101,8 @@ def start(
                                      block_size=block_size, use_graphs=cuda_graphs, tensor_parallel=tensor_parallel,
                                      kv_cache_dtype=kv_cache_dtype, weight_dtype=weight_dtype, weight_max_rows=weight_max_rows, loras=loras,
                                      max_loras=max_loras, max_lora_rank=max_lora_rank,
-                                     guide_table_words=guide_table_words, expert_weight_dtype=expert_weight_dtype)
+                                     guide_table_words=guide_table_words, expert_weight_dtype=expert_weight_dtype,
+                                     moe_max_rows=moe_max_rows)
     try:
         server.run()
     except KeyboardInterrupt:
@@ -120,4 +126,4 @@ def main(
     start(artifact=artifact, port=port, host=host, scheduler="dynamic", max_batch_size=8, max_batch_tokens=8192,
           max_concurrent=128, device=device, kv_cache_fraction=0.85, block_size=16, cuda_graphs=True,
           tensor_parallel=1, kv_cache_dtype="auto", weight_dtype="auto", weight_max_rows=16, lora=None, max_loras=0, max_lora_rank=16,
-          guide_table_words=1 << 18, expert_weight_dtype="auto")
+          guide_table_words=1 << 18, expert_weight_dtype="auto", moe_max_rows=64)

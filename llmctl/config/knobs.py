@@ -82,6 +82,8 @@ class PerfKnobs:
                                    # captured graph; off: the eager MoEMLP module per layer (A/B)
     moe_decode_wq: bool = True     # expert_weight_dtype=fp8 / int4: the routed MLPs stream the quantised experts
                                    # (moe_decode_wq.hip); off: the bf16 experts on the routed kernels (A/B)
+    moe_grouped: bool = True       # moe_max_rows > 64: MoE steps of 65..moe_max_rows rows on the grouped-expert
+                                   # kernels (moe_grouped.hip); off: the eager MoEMLP module per layer (A/B)
 
     def as_dict(self) -> Dict[str, Any]:
         return dataclasses.asdict(self)

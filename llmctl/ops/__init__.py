@@ -34,6 +34,8 @@ from .functional import (
     moe_decode_down_add_rmsnorm,
     moe_decode_ok,
     moe_decode_up_swiglu,
+    moe_grouped_mlp,
+    moe_grouped_ok,
     moe_route,
     paged_attention_decode,
     paged_prefill_attention,
@@ -64,4 +66,5 @@ __all__ = [
     "rmsnorm", "rope_qkv", "rope_flash_attention", "rope_qkv_cache", "sample", "sample_ext", "sample_guided", "guide_state_reset", "sampler_state_reset", "swiglu", "transpose_", "up_swiglu",
     "prompt_logprobs", "rms_rstd", "linear_rowscale", "up_swiglu_rowscale", "linear_acc_",
     "LoRARows", "lora_delta", "MoEExpertTable", "MoEQuantExperts", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",
+    "moe_grouped_ok", "moe_grouped_mlp",
 ]

@@ -65,6 +65,10 @@ TORCH_LIBRARY(llmctl, m) {
   // int4 uint8 [E, N, K / 2] + scale [E, N, K / 128]
   m.def("moe_decode_up_swiglu_wq(Tensor x, Tensor qweight, Tensor scale, Tensor topi) -> Tensor");
   m.def("moe_decode_down_add_rmsnorm_wq(Tensor act, Tensor qweight, Tensor scale, Tensor topi, Tensor topw, Tensor residual, Tensor norm_w, float eps) -> (Tensor, Tensor)");
+  // routed MLP of 1..8192 rows over bf16 experts (moe_grouped.hip): the router for any row count, and
+  // plan -> grouped gate/up + SwiGLU -> grouped down -> weighted combine; y bf16 [M, h]
+  m.def("moe_route_rows(Tensor x, Tensor w_router, int k) -> (Tensor, Tensor)");
+  m.def("moe_grouped_mlp(Tensor x, Tensor up_ptrs, Tensor down_ptrs, Tensor topi, Tensor topw, int F) -> Tensor");
   m.def("sample(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor uniform) -> Tensor");
   m.def("sample_ext(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor uniform, Tensor slot, Tensor rep, Tensor freq, Tensor pres, Tensor nlp, Tensor(a!) counts, Tensor prompt_mask) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("sample_guided(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor uniform, Tensor slot, Tensor rep, Tensor freq, Tensor pres, Tensor nlp, Tensor(a!) counts, Tensor prompt_mask, Tensor guide, Tensor gslot, Tensor guide_cls, Tensor guide_next, Tensor guide_meta, Tensor(b!) guide_state) -> (Tensor, Tensor, Tensor, Tensor)");

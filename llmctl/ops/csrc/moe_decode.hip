@@ -39,65 +39,6 @@ __device__ __forceinline__ bf16x8_t ld16(const unsigned short* p) {
   return *reinterpret_cast<const bf16x8_t*>(p);
 }
 
-// ---- router: bf16-rounded logits -> fp32 softmax -> top-k by repeated arg-max (ties: the lowest
-// expert index), weights renormalised over the picks.  One workgroup per token; wave w computes the
-// logits of experts w, w + 4, ...; wave 0 then holds one expert per lane (E <= 64).
-// The arg-max order is total (NaN compares as a tie, so the lower index wins) and an expert once
-// picked is excluded, so the k indices are always distinct and in [0, E), whatever the inputs.
-__global__ __launch_bounds__(256) void moe_route_kernel(const unsigned short* __restrict__ x,
-                                                        const unsigned short* __restrict__ wr,
-                                                        int* __restrict__ topi, float* __restrict__ topw, int E,
-                                                        int k, int h) {
-  __shared__ float lg[64];
-  const int t = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned short* xr = x + (long)t * h;
-  for (int e = wave; e < E; e += 4) {
-    const unsigned short* w = wr + (long)e * h;
-    float s = 0.f;
-    for (int c = lane * 8; c < h; c += 512) {
-      float a[8], b[8];
-      load8(xr + c, a);
-      load8(w + c, b);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s += a[j] * b[j];
-    }
-    s = wave_sum(s);
-    if (lane == 0) lg[e] = bf2f(f2bf(s));  // linear() returns bf16 before the fp32 softmax
-  }
-  __syncthreads();
-  if (wave != 0) return;
-  const bool valid = lane < E;
-  const float l = valid ? lg[lane] : -INFINITY;
-  const float mx = wave_max(l);
-  const float ex = valid ? __expf(l - mx) : 0.f;
-  const float p = ex / wave_sum(ex);
-  bool used = !valid;
-  int myi = 0;
-  float myw = 0.f;
-  for (int j = 0; j < k; ++j) {
-    float bp = p;
-    int bi = used ? 64 : lane;  // 64: no candidate
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float op = __shfl_xor(bp, o);
-      const int oi = __shfl_xor(bi, o);
-      const bool take = oi < 64 && (bi >= 64 || op > bp || (!(bp > op) && oi < bi));
-      bp = take ? op : bp;
-      bi = take ? oi : bi;
-    }
-    bi = __shfl(bi, 0);
-    bp = __shfl(bp, 0);
-    if (lane == bi) used = true;
-    if (lane == j) myi = bi, myw = bp;
-  }
-  const float tot = wave_sum(myw);  // lanes >= k hold 0
-  if (lane < k) {
-    topi[t * k + lane] = myi;
-    topw[t * k + lane] = myw / tot;
-  }
-}
-
 // ---- routed weight-streaming GEMM: ws[chunk][c][n] = x[row(c)] . W_e[n] over the chunk's K range,
 // for every copy c = t k + j with topi[c] == e (e = blockIdx.z); row(c) = c / xdiv (gate/up: the
 // token's row, xdiv = k; down: the copy's own activation row, xdiv = 1).

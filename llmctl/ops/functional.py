@@ -748,7 +748,33 @@ def moe_route(x, w_router, k: int):
     E, h = w_router.shape
     if moe_decode_ok(x, E, k, h, 128) and w_router.dtype == torch.bfloat16 and w_router.is_contiguous():
         return native().moe_route(x, w_router, k)
+    if (x.dim() == 2 and x.shape[0] > 64 and moe_grouped_ok(x, E, k, h, 128) and w_router.dtype == torch.bfloat16
+            and w_router.is_contiguous()):  # the same kernel, one workgroup per row: bit-identical rows
+        return native().moe_route_rows(x, w_router, k)
     return ref.moe_route(x, w_router, k)
+
+
+def moe_grouped_ok(x, E: int, k: int, h: int, F: int) -> bool:
+    """Can a routed MLP of ``x``'s rows run on the grouped-expert kernels (``csrc/moe_grouped.hip``)?
+    1..8192 bf16 token rows on the GPU with at most 65536 routed copies (rows x k), <= 64 experts,
+    1 <= k <= min(E, 8), hidden and expert width multiples of 128."""
+    return (use_native(x) and x.dim() == 2 and x.dtype == torch.bfloat16 and x.is_contiguous()
+            and 1 <= x.shape[0] <= 8192 and x.shape[0] * k <= 65536 and x.shape[1] == h and 1 <= E <= 64
+            and 1 <= k <= min(E, 8) and h % 128 == 0 and F >= 128 and F % 128 == 0)
+
+
+def moe_grouped_mlp(x, up, down, topi, topw):
+    """``y [M, h]`` in ``x``'s dtype: ``y[t] = sum_j topw[t, j] W_down[e] (silu(g) * u)`` with
+    ``[g; u] = W_up[e] x[t]``, ``e = topi[t, j]`` -- the routed MLP of a prefill chunk, a mixed step or a
+    decode step above 64 rows.  ``up`` / ``down``: ``MoEExpertTable`` of bf16 experts.  The copies are
+    sorted by expert on the device and both projections run as grouped MFMA GEMMs: no host sync, no
+    atomics, shapes known from ``(M, k, E)`` (``csrc/moe_grouped.hip``).  Off the GPU or outside
+    ``moe_grouped_ok``: the fp32 oracle ``ref.moe_grouped_mlp``."""
+    F_ = up.shape[0] // 2
+    if (moe_grouped_ok(x, up.E, topi.shape[1], up.shape[1], F_) and _moe_table_ok(x, up) and _moe_table_ok(x, down)
+            and down.E == up.E and down.shape == (up.shape[1], F_)):
+        return native().moe_grouped_mlp(x, up.ptrs, down.ptrs, topi.contiguous(), topw.contiguous(), F_)
+    return ref.moe_grouped_mlp(x, up.tensors, down.tensors, topi, topw).to(x.dtype)
 
 
 def moe_decode_up_swiglu(x, up, topi):
@@ -869,4 +895,5 @@ __all__ = [
     "decode_linear_add_rmsnorm", "rope_qkv_cache", "paged_prefill_attention", "prefill_work_list", "attn_merge_",
     "rms_rstd", "rowscale_ok", "linear_rowscale", "up_swiglu_rowscale", "linear_acc_",
     "MoEExpertTable", "MoEQuantExperts", "moe_decode_ok", "moe_route", "moe_decode_up_swiglu", "moe_decode_down_add_rmsnorm",
+    "moe_grouped_ok", "moe_grouped_mlp",
 ]

@@ -678,6 +678,25 @@ def moe_decode_mlp(x, experts_up, experts_down, topi, topw, residual, norm_w, ep
     return moe_decode_down_add_rmsnorm(act, experts_down, topi, topw, residual, norm_w, eps)
 
 
+def moe_grouped_mlp(x, experts_up, experts_down, topi, topw) -> torch.Tensor:
+    """fp32 ``y [M, h]``: the routed MLP with no intermediate rounding and no residual,
+    ``y[t] = sum_j topw[t, j] (silu(g) * u) @ experts_down[e]^T`` with ``[g, u] = x[t] @ experts_up[e]^T``,
+    ``e = topi[t, j]`` (slot order)."""
+    M, k = topi.shape
+    act = moe_decode_up_swiglu(x, experts_up, topi)
+    flat = topi.reshape(-1).long()
+    d = torch.zeros(M * k, experts_down[0].shape[0], dtype=torch.float32, device=x.device)
+    for e, w in enumerate(experts_down):
+        c = (flat == e).nonzero().flatten()
+        if c.numel():
+            d[c] = act[c] @ w.float().t()
+    d = d.view(M, k, -1)
+    y = torch.zeros_like(d[:, 0])
+    for j in range(k):
+        y = y + topw[:, j].float().unsqueeze(-1) * d[:, j]
+    return y
+
+
 # ----------------------------------------------------------------------------- per-row LoRA adapters
 def lora_delta(x, lora_idx, lora_a, lora_b, lora_scale) -> torch.Tensor:
     """``delta[m, n] = scale[s] * sum_j (sum_k x[m, k] A[s, j, k]) B[s, n, j]`` with ``s = lora_idx[m]``;

@@ -61,8 +61,14 @@ class InferenceEngine:
                  tuning_cache: Optional[str] = None, perf_knobs: Optional[Dict] = None,
                  kv_cache_dtype: str = "auto", weight_dtype: str = "auto", max_loras: int = 0,
                  max_lora_rank: int = 16, guide_table_words: int = 1 << 18, weight_max_rows: int = 16,
-                 expert_weight_dtype: str = "auto"):
+                 expert_weight_dtype: str = "auto", moe_max_rows: int = 64):
         from llmctl.config import knobs as perf
+
+        # most token rows of a step whose MoE MLPs stay on HIP and in the graph: 64 (the routed-expert
+        # decode kernels only), or up to 8192 (csrc/moe_grouped.hip from 65 rows on: prefill chunks,
+        # mixed steps, decode steps of more than 64 sequences)
+        if isinstance(moe_max_rows, bool) or not isinstance(moe_max_rows, int) or not 64 <= moe_max_rows <= 8192:
+            raise ValueError(f"moe_max_rows must be an integer in 64..8192, got {moe_max_rows!r}")
 
         self.knobs = perf.configure(perf_knobs)  # defaults + perf_knobs + LLMCTL_KNOBS
         if device == "auto":
@@ -177,6 +183,11 @@ class InferenceEngine:
         if self._moe is not None and self._wq is not None and self._moe_q is None:
             log.info("engine: %s decode weights cover the attention projections; the experts stay bf16 "
                      "(expert_weight_dtype quantises them)", self.weight_dtype)
+        self.moe_max_rows = int(moe_max_rows)
+        if self._moe is None and self.moe_max_rows != self.MOE_MAX_ROWS:
+            log.info("engine: moe_max_rows=%d ignored (%s)", moe_max_rows, "a dense model" if not cfg.is_moe
+                     else "the routed-expert kernels do not serve this model here")
+            self.moe_max_rows = self.MOE_MAX_ROWS
         # the eager MoE module sizes the expert segments on the host: graphs only on the routed kernels
         self.use_graphs = use_graphs and self.device.type == "cuda" and (not cfg.is_moe or self._fused_decode())
         self._graphs: Dict[int, Tuple[torch.cuda.CUDAGraph, Dict[str, torch.Tensor]]] = {}
@@ -217,7 +228,7 @@ class InferenceEngine:
         self._np_rng = np.random.default_rng(seed)
         self._pending: Optional[Dict] = None  # an in-flight asynchronous decode step
         self._last_toks: Optional[torch.Tensor] = None  # eager path: the last step's sampled ids
-        self.stats = {"steps": 0, "prefill_tokens": 0, "decode_tokens": 0, "graph_replays": 0}
+        self.stats = {"steps": 0, "prefill_tokens": 0, "decode_tokens": 0, "graph_replays": 0, "moe_grouped_steps": 0}
         log.info("engine: %s on %s, %d KV blocks x %d tokens (%.1f GB)", cfg.name, self.device, num_kv_blocks,
                  block_size, self.kv_cache.nbytes / 1e9)
 
@@ -280,7 +291,19 @@ class InferenceEngine:
     def _moe_fused(self, n: int = 1) -> bool:
         """MoE MLPs of an ``n``-row decode step on the routed-expert kernels (knob
         ``moe_decode_fused`` off: the eager ``MoEMLP`` module, A/B)."""
-        return self._moe is not None and self.knobs.moe_decode_fused and n <= self.MOE_MAX_ROWS
+        if n > self.MOE_MAX_ROWS:
+            return self._moe_grouped(n)
+        return self._moe is not None and self.knobs.moe_decode_fused
+
+    def _moe_grouped(self, n: int) -> bool:
+        """MoE MLPs of an ``n``-row step (prefill, mixed or decode) on the grouped-expert kernels:
+        65..``moe_max_rows`` rows (knob ``moe_grouped`` off: the eager ``MoEMLP`` module, A/B)."""
+        return self._moe is not None and self.knobs.moe_grouped and self.MOE_MAX_ROWS < n <= self.moe_max_rows
+
+    def _moe_grouped_mlp(self, li: int, layer, xn):
+        """The routed MLP of layer ``li`` on the bf16 experts: device-side routing plan, grouped GEMMs."""
+        topi, topw = ops.moe_route(xn, layer.moe.w_router, layer.moe.k)
+        return ops.moe_grouped_mlp(xn, *self._moe[li], topi, topw)
 
     def _graph_ok(self, n: int) -> bool:
         """Does an ``n``-row decode step replay a captured graph?  (MoE: buckets above the routed
@@ -406,8 +429,10 @@ class InferenceEngine:
         return q, k, v
 
     def _mlp(self, layer, xn, li: int = 0, sel=None):
-        if layer.moe is not None:  # routed experts (host-side split sizes: eager, no graphs)
-            return layer.moe(xn)
+        if layer.moe is not None:
+            if self._moe_grouped(xn.shape[0]):
+                return self._moe_grouped_mlp(li, layer, xn)
+            return layer.moe(xn)  # routed experts (host-side split sizes: eager, no graphs)
         if self.cfg.gated_mlp:
             # prefill-sized (T % 256 == 0): the SwiGLU rides on the gate/up GEMM's epilogue
             act = (ops.up_swiglu(xn, layer.w_up, layer.b_up)
@@ -532,6 +557,7 @@ class InferenceEngine:
             xn, res = self._norm(layer, a, res, "mlp")
             x = self._mlp(layer, xn, li, sel)
         self.stats["prefill_tokens"] += T
+        self.stats["moe_grouped_steps"] += int(self._moe_grouped(T))
         if plan.get("score") is not None:
             self._score_rows(plan["score"], x, res)
         if not plan["last"]:
@@ -601,6 +627,7 @@ class InferenceEngine:
         self.stats["prefill_tokens"] += Tp
         self.stats["decode_tokens"] += Td
         self.stats["mixed_steps"] = self.stats.get("mixed_steps", 0) + 1
+        self.stats["moe_grouped_steps"] += int(self._moe_grouped(Tp + Td))
         if pp.get("score") is not None:  # the chunks' rows come first: the plan's row numbers hold
             self._score_rows(pp["score"], x, res)
         rows = torch.tensor(list(pp["last"]) + list(range(Tp, Tp + Td)), device=d)
@@ -814,6 +841,9 @@ class InferenceEngine:
                 xn, res = ops.decode_linear_add_rmsnorm(o.view(o.shape[0], -1), wo, layer.bo, res,
                                                         layer.mlp_norm_w, eps, w_scale=so, lora=rows(li, "wo"))
             nw = layers[li + 1].attn_norm_w if li + 1 < len(layers) else m.final_norm_w
+            if layer.moe is not None and n > self.MOE_MAX_ROWS:  # (65..moe_max_rows rows: the grouped kernels)
+                xn, res = ops.add_rmsnorm(self._moe_grouped_mlp(li, layer, xn), res, nw, eps)
+                continue
             if layer.moe is not None:  # routed experts: all routing stays on the device
                 # (expert_weight_dtype: the fp8 / int4 copies; knob moe_decode_wq off: the bf16 experts, A/B)
                 up_t, down_t = self._moe_q[li] if self._moe_q is not None and self.knobs.moe_decode_wq else self._moe[li]
@@ -1019,6 +1049,7 @@ class InferenceEngine:
         ids, positions, slots, ctx, bt = plan["ids"], plan["positions"], plan["slots"], plan["ctx"], plan["bt"]
         n = len(ids)
         self.stats["decode_tokens"] += n
+        self.stats["moe_grouped_steps"] += int(self._moe_grouped(self._bucket(n) if self._graph_ok(n) else n))
         if self._graph_ok(n):
             g, b = self._stage_and_replay(plan, cont=False)
             return b["logits"][:n]
@@ -1164,11 +1195,12 @@ class InferenceEngine:
         buffer, all bucket rows)."""
         use_knobs(self.knobs)
         cont = bool(plan["cont"])
-        if self._graph_ok(len(plan["positions"])):
+        n = len(plan["positions"])
+        self.stats["moe_grouped_steps"] += int(self._moe_grouped(self._bucket(n) if self._graph_ok(n) else n))
+        if self._graph_ok(n):
             _, b = self._stage_and_replay(plan, cont)
             return b["toks"]
         d = self.device
-        n = len(plan["positions"])
         ids = self._last_toks if cont else torch.as_tensor(np.asarray(plan["ids"], dtype=np.int64)).to(d)
         logits = self._decode_body(ids, torch.as_tensor(np.asarray(plan["positions"], dtype=np.int32)).to(d),
                                    torch.as_tensor(np.asarray(plan["slots"], dtype=np.int64)).to(d),

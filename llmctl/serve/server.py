@@ -133,7 +133,8 @@ class InferenceServer:
                  device: str = "auto", kv_cache_fraction: float = 0.85, block_size: int = 16, use_graphs: bool = True,
                  tensor_parallel: int = 1, engine=None, kv_cache_dtype: str = "auto", weight_dtype: str = "auto",
                  loras: Optional[Dict[str, str]] = None, max_loras: int = 0, max_lora_rank: int = 16,
-                 guide_table_words: int = 1 << 18, weight_max_rows: int = 16, expert_weight_dtype: str = "auto"):
+                 guide_table_words: int = 1 << 18, weight_max_rows: int = 16, expert_weight_dtype: str = "auto",
+                 moe_max_rows: int = 64):
         from fastapi import FastAPI, HTTPException
         from fastapi.middleware.cors import CORSMiddleware
         from fastapi.responses import PlainTextResponse, StreamingResponse
@@ -145,7 +146,8 @@ class InferenceServer:
                                   block_size=block_size, scheduler=scheduler, use_graphs=use_graphs,
                                   kv_cache_dtype=kv_cache_dtype, weight_dtype=weight_dtype,
                                   weight_max_rows=weight_max_rows, max_loras=max(max_loras, len(loras or {})), max_lora_rank=max_lora_rank,
-                                  guide_table_words=guide_table_words, expert_weight_dtype=expert_weight_dtype)
+                                  guide_table_words=guide_table_words, expert_weight_dtype=expert_weight_dtype,
+                                  moe_max_rows=moe_max_rows)
         self.loras = dict(loras or {})  # adapter name -> directory, loaded when the engine starts
         if tensor_parallel != 1 and engine is None:
             raise ValueError("TP serving runs one engine per rank under torchrun: use llmctl.serve.tp "
